@@ -780,6 +780,45 @@ def emit_lines(out):
 
 
 
+DUMP_LIMIT = 64 << 20        # bytes of all --dump-outputs arrays together
+DUMP_SAMPLE = 1 << 17        # reads of the dumped sample (all of them in a smaller batch)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(out_dir, torch, M, res_bytes, tt, tc, n_tc, n_reads):
+    """--dump-outputs: what the timed path handed its caller in its last step -- every read's result (include/mtb.h mtb_result) and its
+    taxID:match_count list -- for a fixed, seeded sample of the batch's reads, as DIR/<name>.npy in float64 (integers) / float32 (the
+    score), at most DUMP_LIMIT bytes together.  Two builds run with the same arguments can be compared file by file.  `taxcnt_off` is
+    where the library placed a list, not part of the answer: the lists themselves are written back to back (`taxcnt_taxid`,
+    `taxcnt_count`, split by `n_taxcnt`).  res_bytes: n_reads x 24 bytes; tt / tc: n_tc entries at the offsets the results name (torch
+    tensors on any device)."""
+    k = min(n_reads, DUMP_SAMPLE)
+    perm = np.random.default_rng(DUMP_SEED).permutation(n_reads)
+    while True:
+        idx = np.sort(perm[:k])                          # (a smaller sample is a prefix of the same permutation)
+        rows = res_bytes.view(n_reads, 24)[torch.from_numpy(idx).to(res_bytes.device)]
+        res = np.frombuffer(rows.cpu().numpy().tobytes(), dtype=M.result_dt)
+        n = res["n_taxcnt"].astype(np.int64)
+        off = res["taxcnt_off"].astype(np.int64)
+        if len(n) and int((off + n).max()) > min(n_tc, tt.numel(), tc.numel()):
+            raise SystemExit(f"dump: a read's taxID:count list ends past the {n_tc} entries the step returned")
+        first = np.zeros(k + 1, np.int64); np.cumsum(n, out=first[1:])
+        nbytes = k * (8 * 7 + 4) + int(first[-1]) * 16
+        if nbytes <= DUMP_LIMIT or k == 1:
+            break
+        k //= 2
+    at = torch.from_numpy(np.repeat(off - first[:-1], n) + np.arange(int(first[-1]), dtype=np.int64)).to(tt.device)
+    arrays = dict(read_index=idx.astype(np.float64), classification=res["classification"].astype(np.float64), score=res["score"].astype(np.float32),
+                  qlen=res["qlen"].astype(np.float64), qlen2=res["qlen2"].astype(np.float64), is_classified=res["is_classified"].astype(np.float64),
+                  flag=res["flag"].astype(np.float64), n_taxcnt=n.astype(np.float64),
+                  taxcnt_taxid=tt[at].cpu().numpy().astype(np.float64), taxcnt_count=tc[at].cpu().numpy().view(np.uint32).astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[rank 0] outputs of the last timed step: {k} of {n_reads} reads, {int(first[-1])} taxID:count entries, "
+        f"{sum(a.nbytes for a in arrays.values())} bytes in {out_dir}")
+
+
 def timed_leg(torch, step_fn, warmup, steps):
     for _ in range(warmup):
         step_fn()
@@ -866,7 +905,12 @@ def main(device=None):
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--dist-backend", default="nccl", help="testing only: gloo lets several ranks share one GPU (RCCL refuses duplicate devices)")
     ap.add_argument("--shared-gpu", action="store_true", help="testing only: every rank uses cuda:0")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's batch: per-read results and taxID:count lists of a "
+                         "fixed, seeded sample of its reads) as DIR/<name>.npy, at most 64 MB together")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch  # before libmtb: both must share one HIP runtime (libamdhip64.so.7)
     rank = int(os.environ.get("RANK", "0")); world_size = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1062,7 +1106,7 @@ def main(device=None):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        n_tc = step()
     barrier()
     dt = time.perf_counter() - t0
     sub_batches_timed = ctx.last_sub_batches if part is None else 0      # of the last timed step (the profiled step and the parity sample overwrite the counter)
@@ -1071,6 +1115,13 @@ def main(device=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     st = ctx.last_stats()
+    if args.dump_outputs and rank == 0:
+        if part is not None:
+            pres, ptt, ptc = last["res"]
+            dump_outputs(args.dump_outputs, torch, M, torch.from_numpy(pres.view(np.uint8)), torch.from_numpy(ptt.view(np.int32)),
+                         torch.from_numpy(ptc.view(np.int32)), len(ptt), args.reads)
+        else:
+            dump_outputs(args.dump_outputs, torch, M, d_res[: args.reads * 24], d_tt, d_tc, n_tc, args.reads)
 
     if part is not None:
         res = last["res"][0]

@@ -142,3 +142,10 @@ def test_headline_line_is_short_whatever_the_detail_holds():
     assert line["roofline"]["frac"] == 0.41 and line["cpu_baseline"]["cores"] == 256 and line["parity_sample"]["mismatches"] == 0
     assert set(line["other_configs"]) == {"paired", "long", "novel", "best_case"} and "roofline" not in line["other_configs"]["long"]
     assert line["detail"] == "bench_detail.json" and line["value"] == 62.12346
+
+
+def test_bench_refuses_zero_timed_steps():
+    """--steps is the number of timed steps (and the last of them is what --dump-outputs writes): there must be one"""
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps must be at least 1" in r.stderr

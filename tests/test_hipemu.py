@@ -166,3 +166,29 @@ def test_bench_line_with_every_leg_stays_under_8_kb(emulated_lib, tmp_path):
             for v in x:
                 yield from fracs(v)
     assert all(f <= 1.0 for f in fracs(detail)), [f for f in fracs(detail) if f > 1.0]
+
+
+def test_bench_dumps_the_outputs_of_its_last_timed_step(emulated_lib, tmp_path):
+    """--dump-outputs: the per-read results and taxID:count lists the timed path returned, as float32 / float64 .npy files under 64 MB; the
+    inputs depend on the arguments alone, so a run of one timed step and a run of two write the same arrays, and they are the arrays the
+    line's classified fraction was taken from (3000 reads: the sample is the whole batch)"""
+    import json
+    import numpy as np
+    env = dict(os.environ, MTB_HIPEMU="1", MTB_LIB=emulated_lib, HIPEMU_THREADS="4")
+    dumps = {}
+    for steps in (1, 2):
+        d = tmp_path / f"steps{steps}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "hipemu", "bench_emulated.py"), "--steps", str(steps), "--warmup", "1", "--reads", "3000",
+                            "--targets", "1.5e6", "--species", "8", "--genome-len", "80000", "--filler-species", "2000", "--no-legs", "--no-parity",
+                            "--dump-outputs", str(d)], env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.split("\n") if ln.startswith("{")][-1])
+        assert line["steps"] == steps
+        arrays = {p.stem: np.load(p) for p in d.iterdir()}
+        assert set(arrays) == {"read_index", "classification", "score", "qlen", "qlen2", "is_classified", "flag", "n_taxcnt", "taxcnt_taxid", "taxcnt_count"}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert (arrays["read_index"] == np.arange(3000)).all() and arrays["n_taxcnt"].sum() == len(arrays["taxcnt_taxid"]) == len(arrays["taxcnt_count"])
+        assert (arrays["is_classified"] != 0).mean() == pytest.approx(line["config"]["classified_fraction"], rel=1e-6) and line["config"]["classified_fraction"] > 0.5
+        dumps[steps] = arrays
+    for name, a in dumps[1].items():
+        assert a.dtype == dumps[2][name].dtype and np.array_equal(a, dumps[2][name]), name
