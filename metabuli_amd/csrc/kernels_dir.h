@@ -468,7 +468,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((PACKED && 
                 } else {
                     const uint32_t bk = mtb_dir_bucket(k[u].value, dv.L, dv.kmer_format);
                     const uint64_t blo = dv.base[bk >> 16] + dv.dir[bk];
-                    const uint32_t room_dn = p - blo > 4u ? 4u : (uint32_t)(p - blo);
+                    /* p < blo: a bucket that starts beyond `limit` (past the last target: lo and hi were clamped to limit below the bucket's start) -- no
+                     * word before p belongs to the query's bucket */
+                    const uint32_t room_dn = p > blo ? (uint32_t)(p - blo > 4u ? 4u : p - blo) : 0u;
                     uint32_t cu = 0, cd = 0;
                     if (cu < room_up && (a0 & 0x1F000000u) == qk32) { cu = 1; if (cu < room_up && (a1 & 0x1F000000u) == qk32) { cu = 2; if (cu < room_up && (a2 & 0x1F000000u) == qk32) { cu = 3; if (cu < room_up && (a3 & 0x1F000000u) == qk32) cu = 4; } } }
                     if (cd < room_dn && (m1 & 0x1F000000u) == qk32) { cd = 1; if (cd < room_dn && (m2 & 0x1F000000u) == qk32) { cd = 2; if (cd < room_dn && (m3 & 0x1F000000u) == qk32) { cd = 3; if (cd < room_dn && (m4 & 0x1F000000u) == qk32) cd = 4; } } }

@@ -144,10 +144,11 @@ def _codons(x):
     return [(int(x) >> (3 * i)) & 7 for i in range(8)]
 
 
-def join_spec(T, values, info, species_of, q_values, q_infos, kmer_format=2, info_mask=0xFFFFFFFF):
-    """-> list of match tuples (qinfo, target_id, species_id, dna, right_end_hamming, hamming), unsorted."""
+def join_spec(T, values, info, species_of, q_values, q_infos, kmer_format=2, info_mask=0xFFFFFFFF, match_last=False):
+    """-> list of match tuples (qinfo, target_id, species_id, dna, right_end_hamming, hamming), unsorted.
+    match_last: the final entry of `values` is a candidate too (a view of an index that is not its last part)."""
     values = np.asarray(values, dtype=np.uint64)
-    cand_values = values[:-1] if len(values) else values          # the last entry of the index is never a candidate
+    cand_values = values if match_last or not len(values) else values[:-1]          # the last entry of the index is never a candidate
     cand_aa = cand_values & AAMASK
     lookup, luts = T["lookup"], T["luts"]
     out = []

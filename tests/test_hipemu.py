@@ -29,9 +29,9 @@ def emulated_lib(tmp_path_factory):
     return build_emulated.build(d)
 
 
-def _run(lib, select, timeout=1500):
+def _run(lib, select, timeout=1500, module="test_gpu_parity.py"):
     env = dict(os.environ, MTB_HIPEMU="1", MTB_LIB=lib)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", "-k", select],
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", module), "-m", "gpu", "-q", "-x", "-p", "no:cacheprovider", "-k", select],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout)
     tail = r.stdout[-3000:]
     assert r.returncode == 0, tail
@@ -105,6 +105,12 @@ def test_long_reads_and_long_runs_on_the_emulator(emulated_lib):
     reading ahead around runs of a dozen candidates"""
     _run(emulated_lib, "(test_fused_batch and sync_long) or (test_long_candidate_runs_are_scanned_by_the_wave and True-1) or test_empty_and_ragged_inputs "
                        "or (test_runs_of_a_dozen_candidates_inside_and_outside_a_window and 11)")
+
+
+def test_join_past_the_last_target_on_the_emulator(emulated_lib):
+    """the window form of the directory join on an index cut to its first 15 % of targets (tests/test_gpu_join_edges.py): queries whose bucket
+    lies past the last target, in tiles staged in LDS, must not take the words before the end as candidates; next to it the sector-random form"""
+    _run(emulated_lib, "test_fused_join_at_the_ends_of_the_index and sync_se and head15 and (window_qt256 or q1w6)", module="test_gpu_join_edges.py")
 
 
 def test_bench_line_of_two_ranks_on_the_emulator(emulated_lib, tmp_path):
