@@ -5,7 +5,9 @@
  * (value NULL or "" = back to the default): that is how bench.py's A/B legs and the tests compare variants inside one process.  An index
  * reads the switches of the context it is opened on, at that moment (directory depth, packed state, chunk size).
  *
- * None of them changes a result: they choose among exact variants, size buffers, or print.                                            */
+ * None of them changes a result -- they choose among exact variants, size buffers, or print -- with one known exception: MTB_SEGM_CONTIG
+ * loses slots (contiguous VRAM is not coherent across kernels, tests/README.md).  tests/test_gpu_scorer_tiers.py runs every other
+ * switch against the oracle; tests/test_abi.py fails for a switch that has no such case.                                               */
 #ifndef MTB_OPTIONS_H
 #define MTB_OPTIONS_H
 #include <cstdint>

@@ -1,6 +1,7 @@
 """The C-ABI library loads and exports every function include/mtb.h declares
 (no compute calls here: there is no GPU in the CPU test run)."""
 import ctypes as C
+import inspect
 import os
 import re
 
@@ -103,3 +104,46 @@ def test_share_record_size_matches_the_binding(tmp_path):
     exe = tmp_path / "s"
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
     assert int(subprocess.check_output([str(exe)]).decode()) == M.SHARE_BYTES
+
+
+def _function_source(path, name):
+    src = open(path).read()
+    m = re.search(r"^def " + re.escape(name) + r"\(.*?(?=^(?:def |@|class |# -{10})|\Z)", src, flags=re.S | re.M)
+    assert m, f"{os.path.basename(path)} has no {name}"
+    return m.group(0)
+
+
+def test_every_experiment_switch_has_a_parity_case():
+    """every MTB_* switch of mtb_options.h is run against the oracle by a GPU test (test_gpu_scorer_tiers.SWITCH_CASES names it), or is
+    exempt with a reason: a switch added later without a parity case fails here"""
+    names = re.findall(r'MTB_OPT\("(MTB_\w+)"', open(os.path.join(ROOT, "metabuli_amd", "csrc", "mtb_options.h")).read())
+    assert len(names) == len(set(names)) and len(names) >= 34
+    import test_gpu_scorer_tiers as T
+    assert set(T.SWITCH_CASES) | set(T.SWITCH_EXEMPT) == set(names), set(names) ^ (set(T.SWITCH_CASES) | set(T.SWITCH_EXEMPT))
+    assert not set(T.SWITCH_CASES) & set(T.SWITCH_EXEMPT)
+    assert all(T.SWITCH_EXEMPT.values()) and "MTB_SEGM_CONTIG" in T.SWITCH_EXEMPT
+    def flat(v):
+        if isinstance(v, str):
+            yield v
+        elif isinstance(v, (list, tuple)):
+            for x in v:
+                yield from flat(x)
+    for name, where in T.SWITCH_CASES.items():
+        for ref in [w.strip() for w in where.split(",")]:
+            if "::" in ref:                          # a case of an existing GPU test: the switch is named in that test's own code
+                fname, func = ref.split("::")
+                assert f'"{name}"' in _function_source(os.path.join(ROOT, "tests", fname), func), (name, ref)
+            else:                                    # a row of a case table that the named test itself (decorators included) runs
+                fn = getattr(T, ref, None)
+                assert callable(fn), (name, ref)
+                tables = set(re.findall(r"\b([A-Z][A-Z0-9_]*(?:_CASES|_VARIANTS))\b", inspect.getsource(fn))) & set(vars(T)) - {"SWITCH_CASES"}
+                assert name in {x for t in tables for x in flat(getattr(T, t))}, (name, ref, sorted(tables))
+
+
+def test_stride_matrix_covers_every_bucket_and_cap():
+    """the stride matrix of test_gpu_scorer_tiers.py names every k_score_fast instantiation, the two non-fast outcomes and every LDS cap
+    of the generic slot k_score (each case asserts on the GPU that it lands where it is named)"""
+    import test_gpu_scorer_tiers as T
+    assert {c[4] for c in T.STRIDE_CASES} >= {"fast<2>", "fast<3>", "fast<4>", "fast<5,6,false>", "fast<3,3,true>", "fast<4,4,true>",
+                                               "fast<5,6,true>", "generic", "exact"}
+    assert {c[5] for c in T.STRIDE_CASES} >= {144, 160, 224, 288, 320}
