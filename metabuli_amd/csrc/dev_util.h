@@ -9,6 +9,11 @@
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }
 __device__ __forceinline__ uint64_t lanemask_lt() { return (1ull << lane_id()) - 1ull; }
 
+/* lane l's value, wave-uniform (l is wave-uniform too); ordering of LDS accesses between the lanes of one wavefront */
+__device__ __forceinline__ int32_t rl_i(int32_t v, int32_t l) { return __builtin_amdgcn_readlane(v, l); }
+__device__ __forceinline__ float rl_f(float v, int32_t l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+__device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+
 /* inclusive scan across the 64 lanes of a wavefront */
 template <typename T>
 __device__ __forceinline__ T wave_inclusive_scan(T v) {

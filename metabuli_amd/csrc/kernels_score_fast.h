@@ -48,10 +48,6 @@ __device__ unsigned long long mtb_fast_reasons[32];          /* [8..]: cycles pe
 #define MTB_FAST_MARK(k) do {} while (0)
 #endif
 
-__device__ __forceinline__ int32_t rl_i(int32_t v, int32_t l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ float rl_f(float v, int32_t l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ void wave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
-
 /* wave reductions with DPP row shifts / broadcasts (6 VALU + 1 readlane; a __shfl_xor butterfly is 6 ds_bpermute round trips).
  * row_shr:n = 0x110+n inside rows of 16 lanes, row_bcast:15 = 0x142 (rows 1 and 3), row_bcast:31 = 0x143 (rows 2 and 3); lanes a
  * step does not reach combine their value with itself.  The result is wave-uniform. */

@@ -51,9 +51,6 @@ __device__ unsigned long long mtb_long_cycles[16];
 #else
 #define MTB_LP_MARK(k) do {} while (0)
 #endif
-__device__ __forceinline__ int32_t lrl_i(int32_t v, int32_t l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ float lrl_f(float v, int32_t l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-__device__ __forceinline__ void lwave_fence() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
 
 /* combineMatchPaths' order inside one species: a before b (ties by emission order = index of the end match) */
 __device__ __forceinline__ bool lpath_before(const mtb_lpath &a, const mtb_lpath &b) {
@@ -311,13 +308,13 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
                         const int32_t ge = r2 ? (int32_t)__builtin_ctzll(r2) : nin;
                         if (!(r2 != 0 || ends)) break;                            /* trailing group may go on in the next window */
                         multi = true;
-                        const uint32_t posP = (uint32_t)lrl_i((int32_t)pos, ps), posG = (uint32_t)lrl_i((int32_t)pos, gs);
+                        const uint32_t posP = (uint32_t)rl_i((int32_t)pos, ps), posG = (uint32_t)rl_i((int32_t)pos, gs);
                         const int32_t s = (int32_t)(posG - posP) / 3;
                         const bool ok = s > 0 && s <= sp.max_codon_shift;
                         const bool inG = lane >= gs && lane < ge;
                         int32_t best = -1; float best_sc = 0.0f; uint64_t conn = 0;
                         if (ok) for (int32_t cu = ps; cu < pe; cu++) {
-                            const uint32_t dcu = (uint32_t)lrl_i((int32_t)dna, cu); const float scu = lrl_f(p_score, cu);
+                            const uint32_t dcu = (uint32_t)rl_i((int32_t)dna, cu); const float scu = rl_f(p_score, cu);
                             const bool c = inG && mtb_consecutive(dcu, dna, s, fwd, sp.kmer_format);
                             if (c && scu > best_sc) { best = cu; best_sc = scu; }
                             if (__ballot(c)) conn |= 1ull << cu;
@@ -341,12 +338,12 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
                 }
                 if (!done) {
                     /* the block goes on: the last processed group opens the next window with its path state */
-                    lwave_fence();
+                    wave_fence();
                     if (lane >= ps && lane < pe) {
                         s_carry[wv][lane - ps][0] = p_start; s_carry[wv][lane - ps][1] = __float_as_int(p_score); s_carry[wv][lane - ps][2] = p_ham;
                         s_carry[wv][lane - ps][3] = p_depth; s_carry[wv][lane - ps][4] = (int32_t)p_sreh;
                     }
-                    lwave_fence();
+                    wave_fence();
                     carry_n = pe - ps; base += (uint32_t)ps;
                 }
             }
@@ -432,7 +429,7 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
                         const int32_t q = a >> 6, l = a & 63;
                         const int32_t vs = q == 0 ? a_st[0] : q == 1 ? a_st[1] : q == 2 ? a_st[2] : a_st[3];
                         const int32_t ve = q == 0 ? a_en[0] : q == 1 ? a_en[1] : q == 2 ? a_en[2] : a_en[3];
-                        cst = lrl_i(vs, l); cen = lrl_i(ve, l);
+                        cst = rl_i(vs, l); cen = rl_i(ve, l);
                     } else { const mtb_lpath c = s_path[s_acc[lo + a]]; cst = c.start; cen = c.end; }
                     if (!__any(!drop)) break;
                     if (!drop) against(cst, cen);
@@ -442,14 +439,14 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
                     const uint64_t sm = __ballot(!drop && !taken);
                     if (!sm) break;
                     const int32_t f = (int32_t)__builtin_ctzll(sm);
-                    const int32_t fst = lrl_i(p.start, f), fen = lrl_i(p.end, f);
-                    const float fsc = lrl_f(p.score, f);
+                    const int32_t fst = rl_i(p.start, f), fen = rl_i(p.end, f);
+                    const float fsc = rl_f(p.score, f);
                     if (na < 256) {
 #pragma unroll
                         for (int q = 0; q < 4; q++) if (q == (na >> 6) && lane == (na & 63)) { a_st[q] = fst; a_en[q] = fen; }
                     } else {
                         if (lane == f) { s_path[pi] = p; s_acc[lo + na] = (uint16_t)pi; }
-                        lwave_fence();
+                        wave_fence();
                     }
                     na++; score += fsc;
                     if (lane == f) taken = true;

@@ -85,13 +85,30 @@ __global__ __launch_bounds__(64) void k_unpack_reads(const uint8_t *__restrict__
     }
 }
 
-struct DevBuf { void *p = nullptr; size_t cap = 0; };
+/* what an entry is, said by its first ensure(): BUF_IO = a call's inputs / outputs (host-buffer entry points), not workspace; BUF_FIXED = workspace that does not grow with the sub-batch (the slab pool) */
+enum BufKind : uint8_t { BUF_WORK = 0, BUF_IO = 1, BUF_FIXED = 2 };
+struct DevBuf { void *p = nullptr; size_t cap = 0; BufKind kind = BUF_WORK; };
 /* the slab pool of the generic scorer's large-segment launches (reads beyond every LDS budget: 2 of 200 k long reads on the bench's index).  Round 6: 16 GiB
  * instead of 48 -- the 32 GiB went to the long-read sub-batches (200 k x 10 kb: two of 100 k reads instead of four of 50 k; denser sorted queries) */
 #define MTB_SLAB_POOL_MAX (16ull << 30)
 #define MTB_LONG_WIN_MAX_PER_Q 24.0   /* long reads: targets per query metamer up to which the window form is taken without being asked for */
 #define MTB_OVF_STRIPES 256u
 
+/* The context's device scalars (mtb_ctx::d_scal), one 8-byte word per name.  Names cleared or read back with ONE call stay adjacent; two names share a word only where noted. */
+enum Scal : uint32_t {
+    SC_JOIN_COUNT = 0, SC_JOIN_OVERFLOW = 1,     /* dev_join: matches (slot modes: overflow entries) found; the kernels' overflow flag */
+    SC_BAD_SEQ = SC_JOIN_OVERFLOW,               /* k_slot_place / k_count_reads: a sequenceID outside the batch.  Shared: k_slot_place runs in the join's place (mtb_part_score); count_reads reads its flag back before it returns */
+    SC_N_LARGE = 2, SC_MAX_SEG = 3,              /* exact segments (dev_segsort, score_join_order): segments beyond the LDS sort, the largest segment */
+    SC_MAX_LEN = 4, SC_OPEN_CARRY = 5,           /* dev_extract: longest read; index open (decode_chunked): last flat value of the previous chunk */
+    SC_N_GENERIC = 6, SC_LONG_N_SECOND = 7,      /* reads a listing scorer left to the generic kernel (take_generic_reads); dev_score_long: reads flagged for its second launch */
+    SC_EXTRACT = 8, SC_WIN_STATS = 16,           /* 8 words, struct ExtractCounters; 2 words: the window join's tiles with a window / outside it */
+    SC_N_UNGROUPED = 18, SC_MAX_BIG_SEG = 19, SC_N_DEFERRED = 20, SC_DEFER_N_LARGE = 21,     /* score_fixed_slots' deferred reads: ungrouped overflow entries, largest segment, number, segments beyond the LDS sort */
+    SC_SCORE_WORK = 22, SC_LONG_WORK = 24,       /* work counters: dev_score's two passes (2 words), k_score_long */
+    SC_LS_N_FAIL = 25, SC_LS_N_ALL = 26, SC_LS_MAX_SEG = 27, SC_LS_WORK = 28,    /* long-read slot path: reads beyond k_seg_order's LDS tables, matches of the range, those reads' largest segment, k_seg_order's work counter */
+    SC_OPEN_FLAGS = 29, SC_WORDS = 30            /* index open: the directory kernels' two 32-bit flags */
+};
+struct ExtractCounters { uint64_t records /* allocated, incl. blank tails */, overflow, real, max_q /* most metamers of a read */, off_max_q, off_reads, off_max_len /* marked-read statistics */, spare; };
+static_assert(sizeof(ExtractCounters) == 8 * (SC_WIN_STATS - SC_EXTRACT) && SC_WIN_STATS + 2 <= SC_N_UNGROUPED && SC_SCORE_WORK + 2 <= SC_LONG_WORK && SC_OPEN_FLAGS < SC_WORDS, "scalar names overlap or leave the block");
 struct mtb_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -101,8 +118,7 @@ struct mtb_ctx {
     std::mutex bufs_mu;              /* the buffer table may be grown from a helper thread (mtb_ctx_reserve) while the context's thread opens an index */
     std::mutex reserve_mu;           /* held by mtb_ctx_reserve for its whole run */
     std::atomic<bool> reserve_cancel{false};     /* an index open on this context found device memory short: a running reservation stops after its current buffer, a new one does nothing, and what was reserved is handed back (open_make_room) */
-    uint64_t *d_scal = nullptr;      /* [0] match counter, [1] overflow, [2] n_large, [3] max_seg, [4] max_len, [5] n_big */
-    uint64_t *d_xscal = nullptr;     /* = d_scal + 8: single-pass extraction counters */
+    uint64_t *d_scal = nullptr;      /* SC_WORDS device scalars, one 8-byte word per Scal name: scal<T>(c, SC_X) */
     unsigned long long *d_ovfctr = nullptr;      /* MTB_OVF_STRIPES counters of the striped overflow list, 64 bytes apart (JoinSegArgs::ovf_stripes) */
     uint64_t ovf_region = 0, ovf_max_region = 0; /* entries per region in the last slot-mode join; fullest region */
     hipEvent_t ev[8];
@@ -114,7 +130,7 @@ struct mtb_ctx {
     std::vector<mtb_ctx *> lanes;    /* extra stream contexts (mtb_ctx_set_streams) */
     bool is_lane = false;            /* lanes share the parent's tables  */
     uint32_t seg_epoch = 0;          /* tag of the live slots in the "segm" buffer (1..MTB_SLOT_EPOCHS) */
-    const void *seg_clean_p = nullptr; size_t seg_clean_cap = 0;     /* the allocation the epoch count belongs to: the one prepare_slots last cleared (another pointer or size, e.g. after mtb_ctx_reserve grew or created "segm", holds stale bytes) */
+    const void *seg_clean_p = nullptr; size_t seg_clean_cap = 0;     /* the allocation the epoch count belongs to: the one make_slots last cleared (another pointer or size, e.g. after mtb_ctx_reserve grew or created "segm", holds stale bytes) */
     double extract_yield = 0.0;      /* metamers per base of the previous batch (single-pass extraction buffer sizing) */
     uint64_t part_n_reads = 0; uint32_t part_max_len = 0;   /* batch state between mtb_part_extract and mtb_part_score */
     int part_mode = 0; uint32_t part_max_q = 0; uint64_t part_nk_real = 0;      /* part_mode 1: the batch's metamers carry ordinals, the matches come home into slot segments */
@@ -124,8 +140,7 @@ struct mtb_ctx {
     uint64_t ws_max_sub_bases = 0;   /* bases of the largest sub-batch since the workspace was last released */
     int ws_seq_mode = 0;             /* the buffer sets of short and long reads differ: a change of mode releases the workspace */
     uint32_t last_sub_batches = 0;
-    bool fast_used = false;          /* the last dev_score call launched k_score_fast (its slow-list count sits in d_scal[6]) */
-    bool no_lslot = false;           /* classify_one is redoing a long-read range on the exact-segment path */
+    bool fast_used = false;          /* a scorer that lists what it leaves to the generic kernel ran (dev_score's k_score_fast, dev_score_long): SC_N_GENERIC holds the count (take_generic_reads) */
     const mtb_kmer *last_sorted = nullptr; uint64_t last_sorted_n = 0;       /* the last fused slot-path batch's sorted metamers (mtb_ctx_join_footprint) */
     /* what the join leaves dead until the next batch's extraction -- the metamer buffer that does NOT hold the sorted list, both digit arrays: the scorer's large
      * per-batch temporaries (the grouped overflow list, the deferred reads' segments) are carved out of them (scratch()) instead of being allocations of their own:
@@ -152,14 +167,16 @@ struct mtb_ctx {
     uint32_t lslot_tf_start = 1;                     /* long-read slot ranges: tail factor the next batch starts with (1 = a quarter of the metamers, 4 = all) */
     MtbOptions opt;                                  /* the experiment / diagnosis switches: the MTB_* environment at mtb_ctx_create, mtb_ctx_set_option afterwards (mtb_options.h) */
 };
-/* buffers that carry a call's inputs / outputs (host-buffer entry points) are not workspace */
-static bool is_io_buf(const std::string &n) { return n == "bases" || n == "offs" || n == "bases2" || n == "offs2" || n == "results" || n == "resultsb" || n == "tctax" || n == "tccnt" || n.compare(0, 2, "pk") == 0; }
-static size_t held_bytes(mtb_ctx *c) { std::lock_guard<std::mutex> lk(c->bufs_mu); size_t b = 0; for (auto &kv : c->bufs) if (!is_io_buf(kv.first)) b += kv.second.cap; return b; }
-/* the part of it that grows with the sub-batch (the slab pool of the large-segment scorer is bounded on its own) */
-static size_t scaling_bytes(mtb_ctx *c) { std::lock_guard<std::mutex> lk(c->bufs_mu); size_t b = 0; for (auto &kv : c->bufs) if (!is_io_buf(kv.first) && kv.first != "slabs") b += kv.second.cap; return b; }
+template <typename T> static T *scal(mtb_ctx *c, Scal s) { return (T *)(c->d_scal + s); }
+static hipError_t scal_clear(mtb_ctx *c, Scal first, uint32_t words = 1) { return hipMemsetAsync(c->d_scal + first, 0, 8 * (size_t)words, c->stream); }
+/* The buffer table is touched only by ensure / ensure_placed / release / buf_get and by the whole-table walks, all under bufs_mu. */
+static DevBuf buf_get(mtb_ctx *c, const std::string &name) { std::lock_guard<std::mutex> lk(c->bufs_mu); auto it = c->bufs.find(name); return it == c->bufs.end() ? DevBuf() : it->second; }
+static size_t buf_cap(mtb_ctx *c, const char *name) { return buf_get(c, name).cap; }
+/* workspace held: all of it (upto = BUF_FIXED), or only what grows with the sub-batch (upto = BUF_WORK) */
+static size_t held_bytes(mtb_ctx *c, BufKind upto) { std::lock_guard<std::mutex> lk(c->bufs_mu); size_t b = 0; for (auto &kv : c->bufs) if (kv.second.kind == BUF_WORK || kv.second.kind == upto) b += kv.second.cap; return b; }
 static void release_workspace(mtb_ctx *c) {
     std::lock_guard<std::mutex> lk(c->bufs_mu);
-    for (auto &kv : c->bufs) if (kv.second.p && !is_io_buf(kv.first)) { hipError_t e = hipFree(kv.second.p); (void)e; kv.second.p = nullptr; kv.second.cap = 0; }
+    for (auto &kv : c->bufs) if (kv.second.p && kv.second.kind != BUF_IO) { hipError_t e = hipFree(kv.second.p); (void)e; kv.second.p = nullptr; kv.second.cap = 0; }
     c->ws_per_base = 0.0; c->ws_max_sub_bases = 0;
     c->seg_clean_p = nullptr; c->seg_clean_cap = 0;       /* a later "segm" at the same address is not the buffer that was cleared */
 }
@@ -219,17 +236,18 @@ struct mtb_index {
     void *ipc_stage[4] = {nullptr, nullptr, nullptr, nullptr};       /* mtb_index_export: copies of the arrays too small for an inter-process handle of their own */
 };
 
+enum ResKind { RES_ROWS = 0, RES_TAX = 1, RES_CNT = 2 };    /* the two device-side result sets of the asynchronous path: rows, packed taxID:count lists */
+static const char *res_name(ResKind k, int set) { static const char *const names[2][3] = {{"results", "tctax2", "tccnt2"}, {"resultsb", "tctax2b", "tccnt2b"}}; return names[set ? 1 : 0][k]; }
 template <typename T>
-static mtb_status ensure(mtb_ctx *c, const char *name, size_t elems, T **out) {
+static mtb_status ensure(mtb_ctx *c, const char *name, size_t elems, T **out, BufKind kind = BUF_WORK) {
     if (c->down_pending) {
         /* asynchronous results (mtb_classify_batch_packed_async): whoever asks for a buffer that queued copies still read waits for them first
          * (the asynchronous path itself asks for the other set) */
-        static const char *const sets[2][3] = {{"results", "tctax2", "tccnt2"}, {"resultsb", "tctax2b", "tccnt2b"}};
         const int fl = c->res_set ^ 1;
-        if (!strcmp(name, sets[fl][0]) || !strcmp(name, sets[fl][1]) || !strcmp(name, sets[fl][2])) { HIPCHK(hipEventSynchronize(c->down_done)); c->down_pending = false; }
+        if (!strcmp(name, res_name(RES_ROWS, fl)) || !strcmp(name, res_name(RES_TAX, fl)) || !strcmp(name, res_name(RES_CNT, fl))) { HIPCHK(hipEventSynchronize(c->down_done)); c->down_pending = false; }
     }
     std::lock_guard<std::mutex> lk(c->bufs_mu);
-    DevBuf &b = c->bufs[name];
+    DevBuf &b = c->bufs.emplace(name, DevBuf{nullptr, 0, kind}).first->second;      /* what the entry is stays what its first request said */
     size_t bytes = elems * sizeof(T);
     if (bytes == 0) bytes = 64;
     if (b.cap < bytes) {
@@ -283,7 +301,9 @@ __global__ __launch_bounds__(256) void k_clear_words(uint64_t *p, uint64_t n_wor
     MTB_END_RELEASE();
 }
 static mtb_status ensure_placed(mtb_ctx *c, const char *name, size_t elems, mtb_slot16 **out) {
+    std::unique_lock<std::mutex> lk(c->bufs_mu);     /* held while this function allocates the entry itself -- a probe's seconds included: a reservation thread waits in ensure() that long, once per big slot buffer, which is accepted; let go of before the plain path (ensure locks on its own) */
     DevBuf &b = c->bufs[name];
+    auto plain = [&] { lk.unlock(); return ensure(c, name, elems, out); };
     const size_t bytes = std::max<size_t>(elems * sizeof(mtb_slot16), 64);
     /* experiment switch (tests/test_gpu_contig.py, profiles/r03_notes.md): the slot buffer -- of ANY size -- from physically
      * contiguous VRAM, the configuration in which round 2 saw pair scores differ from the oracle's */
@@ -303,7 +323,7 @@ static mtb_status ensure_placed(mtb_ctx *c, const char *name, size_t elems, mtb_
      * (profiles/r03_e2e_driver_30Mreads.txt).  A process with a long allocation history of its own (bench.py under torch's caching
      * allocator) turns it on. */
     const bool no_probe = c->opt.no_placement_probe != 0, env_probe = c->opt.placement_probe != 0;
-    if (b.cap >= bytes || bytes < (8ull << 30) || no_probe || !(c->placement_probe || env_probe)) return ensure(c, name, elems, out);
+    if (b.cap >= bytes || bytes < (8ull << 30) || no_probe || !(c->placement_probe || env_probe)) return plain();
     if (b.p) { hipError_t e = hipFree(b.p); (void)e; b.p = nullptr; b.cap = 0; }
     const size_t want = bytes + bytes / 16 + 256;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -356,7 +376,7 @@ static mtb_status ensure_placed(mtb_ctx *c, const char *name, size_t elems, mtb_
     guard.armed = false;
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     for (void *q : pads) { hipError_t e = hipFree(q); (void)e; }
-    if (held.empty()) return ensure(c, name, elems, out);              /* not even one candidate fitted: the plain path reports the error */
+    if (held.empty()) return plain();            /* not even one candidate fitted: the plain path reports the error */
     size_t pick = 0;
     for (size_t k = 1; k < held.size(); k++) if (held[k].ms < held[pick].ms) pick = k;
     for (size_t k = 0; k < held.size(); k++) if (k != pick) { hipError_t e = hipFree(held[k].p); (void)e; }
@@ -394,8 +414,7 @@ mtb_status mtb_ctx_create(int device, void *stream, mtb_ctx **out) {
     mtb_build_tables(&c->h_tabs);
     HIPCHK(hipMalloc((void **)&c->d_tabs, sizeof(mtb_tables)));
     HIPCHK(hipMemcpy(c->d_tabs, &c->h_tabs, sizeof(mtb_tables), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc((void **)&c->d_scal, 24 * sizeof(uint64_t)));      /* [16..23]: the join's tile statistics */
-    c->d_xscal = c->d_scal + 8;
+    HIPCHK(hipMalloc((void **)&c->d_scal, SC_WORDS * sizeof(uint64_t)));
     HIPCHK(hipMalloc((void **)&c->d_ovfctr, MTB_OVF_STRIPES * 64));
     for (int i = 0; i < 8; i++) HIPCHK(hipEventCreate(&c->ev[i]));
     memset(&c->stats, 0, sizeof(c->stats));
@@ -409,7 +428,7 @@ void mtb_ctx_destroy(mtb_ctx *c) {
     c->lanes.clear();
     hipError_t e = hipSetDevice(c->device); (void)e;
     e = hipStreamSynchronize(c->stream);
-    for (auto &kv : c->bufs) if (kv.second.p) e = hipFree(kv.second.p);
+    { std::lock_guard<std::mutex> lk(c->bufs_mu); for (auto &kv : c->bufs) if (kv.second.p) e = hipFree(kv.second.p); }
     if (c->d_tabs && !c->is_lane) e = hipFree(c->d_tabs);
     if (c->d_scal) e = hipFree(c->d_scal);
     if (c->d_ovfctr) e = hipFree(c->d_ovfctr);
@@ -465,8 +484,7 @@ mtb_status mtb_ctx_set_streams(mtb_ctx *c, int n) {
         mtb_ctx *l = new mtb_ctx();
         l->device = c->device; l->is_lane = true; l->d_tabs = c->d_tabs; l->h_tabs = c->h_tabs; l->profiling = c->profiling; l->placement_probe = c->placement_probe; l->opt = c->opt;
         HIPCHK(hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
-        HIPCHK(hipMalloc((void **)&l->d_scal, 24 * sizeof(uint64_t)));
-        l->d_xscal = l->d_scal + 8;
+        HIPCHK(hipMalloc((void **)&l->d_scal, SC_WORDS * sizeof(uint64_t)));
         HIPCHK(hipMalloc((void **)&l->d_ovfctr, MTB_OVF_STRIPES * 64));
         for (int i = 0; i < 8; i++) HIPCHK(hipEventCreate(&l->ev[i]));
         memset(&l->stats, 0, sizeof(l->stats));
@@ -504,61 +522,69 @@ static uint64_t extract_cap_guess(const mtb_ctx *c, const mtb_params *p, uint64_
     return std::min<uint64_t>(extract_bound(n_bases, grid), (uint64_t)((double)n_bases * guess * 1.15) + 4096 + (uint64_t)grid * 64);
 }
 
-/* extract.  Result in buffer "kmersA".  Two passes (counts -> offsets -> emit) give the reference's emission order
- * (stage API); `single_pass` (fused path, n_bases = bases of the batch) runs the arithmetic once and lets every
- * wave reserve its output with an atomic: run order arbitrary, which the radix sort does not mind. */
-static mtb_status dev_extract(mtb_ctx *c, const mtb_params *p, const char *d_bases, const uint64_t *d_offs, const char *d_bases2,
-                              const uint64_t *d_offs2, uint64_t n_reads, mtb_kmer **out, uint64_t *count, int32_t *d_qlen,
-                              int32_t *d_qlen2, uint32_t *max_len, bool single_pass = false, uint64_t n_bases = 0,
-                              uint64_t *real_count = nullptr, bool tag_ord = false, uint32_t *max_q = nullptr, uint16_t **dig = nullptr,
-                              uint32_t *d_counts = nullptr /* single pass: metamers per read (long-read slot path) */,
-                              uint64_t *n_bases_exact = nullptr /* single pass: bases of the read range, from its offsets */,
-                              uint8_t *d_off = nullptr /* tagged single pass: reads the slot records cannot hold are marked here ... */,
-                              uint64_t *off_stats = nullptr /* ... [0] most metamers of an unmarked read, [1] marked reads, [2] longest unmarked read */) {
+struct Reads {                            /* a batch, or a read range of one, on the device */
+    const char *d_bases = nullptr; const uint64_t *d_offs = nullptr; const char *d_bases2 = nullptr; const uint64_t *d_offs2 = nullptr; uint64_t n_reads = 0;
+    Reads range(uint64_t lo, uint64_t cnt) const { Reads r = *this; r.d_offs += lo; if (r.d_offs2) r.d_offs2 += lo; r.n_reads = cnt; return r; }
+};
+struct ReadLens { const int32_t *d_ql = nullptr, *d_ql2 = nullptr; uint32_t max_len = 0; };         /* per-read lengths as the extractor left them; the longest read */
+struct ResultSink { mtb_result *d_res = nullptr; int32_t *d_tc_tax = nullptr; uint32_t *d_tc_cnt = nullptr; uint64_t tc_cap = 0, tc_base = 0; };     /* a read range's rows and taxID:count slots: capacity, first slot in the caller's arrays */
+struct ExtractOpts {
+    bool single_pass = false;             /* fused path: the arithmetic once, every wave reserves its output with an atomic (run order arbitrary, which the radix sort does not mind) */
+    bool tag_ordinals = false, want_digits = false;       /* single pass: the metamer's ordinal in its read rides in qinfo (slot paths); the first radix pass's digits in buffer "digA" */
+    bool want_max_len = true;             /* read the longest read's length back */
+    uint32_t *d_counts = nullptr;         /* single pass: metamers per read (long-read slot path) */
+    uint8_t *d_off_reads = nullptr;       /* tagged single pass: reads the slot records cannot hold are marked here */
+};
+struct Extracted {
+    mtb_kmer *d_k = nullptr; uint64_t nk = 0, nk_real = 0;      /* buffer "kmersA"; records (the single pass counts its blank tail records too), metamers */
+    uint32_t max_len = 0, max_q = 0;      /* longest read; single pass: most metamers of a read */
+    uint16_t *d_dig = nullptr; uint64_t n_bases = 0;            /* single pass: bases of the read range, from its offsets */
+    uint64_t off_max_q = 0, off_reads = 0, off_max_len = 0;     /* d_off_reads: most metamers of an unmarked read, marked reads, longest unmarked read */
+};
+/* extract.  Two passes (counts -> offsets -> emit) give the reference's emission order (stage API); the fused path asks for the single pass. */
+static mtb_status dev_extract(mtb_ctx *c, const mtb_params *p, const Reads &rd, int32_t *d_qlen, int32_t *d_qlen2, const ExtractOpts &opt, Extracted *ex) {
+    const uint64_t n_reads = rd.n_reads;
     if (n_reads >= (1ull << 29)) return fail(MTB_ERR_ARG, "more than 2^29-1 reads per batch (sequenceID is 29 bits, Kmer.h:13)");
     if (p->kmer_format != 1 && p->kmer_format != 2) return fail(MTB_ERR_UNSUPPORTED, "only kmer_format 1 and 2 are implemented");
     if (p->syncmer && (p->smer_len < 1 || p->smer_len > 8)) return fail(MTB_ERR_ARG, "smer_len out of range");
-    *count = 0; *out = nullptr;
-    if (real_count) *real_count = 0;
+    *ex = Extracted();
     if (n_reads == 0) return MTB_OK;
-    ExtractArgs a{d_bases, d_offs, d_bases2, d_offs2, n_reads, p->seq_mode, p->syncmer, p->smer_len, p->kmer_format, (single_pass && tag_ord) ? 1 : 0, sort_msd_first(c) ? 54 : 34};
+    const bool single_pass = opt.single_pass;
+    ExtractArgs a{rd.d_bases, rd.d_offs, rd.d_bases2, rd.d_offs2, n_reads, p->seq_mode, p->syncmer, p->smer_len, p->kmer_format, (single_pass && opt.tag_ordinals) ? 1 : 0, sort_msd_first(c) ? 54 : 34};
     /* grid sweep, 10 M reads: 7424 workgroups 23.5 ms, 16384 18.7, 65536 17.3, 262144 17.7 (and more blank tail records) */
     uint32_t grid = (uint32_t)std::min<uint64_t>(n_reads, 256ull * 256);
-    HIPCHK(hipMemsetAsync(c->d_scal + 4, 0, 8, c->stream));
+    HIPCHK(scal_clear(c, SC_MAX_LEN));
+    uint64_t &n_bases = ex->n_bases;
     if (single_pass) {
-        /* exact number of bases of this read range (the caller's figure may be an estimate) */
+        /* exact number of bases of this read range (what the caller knows may be an estimate) */
         uint64_t o[2];
-        STCHK(d2h(c, &o[0], d_offs, 8)); STCHK(d2h(c, &o[1], d_offs + n_reads, 8));
+        STCHK(d2h(c, &o[0], rd.d_offs, 8)); STCHK(d2h(c, &o[1], rd.d_offs + n_reads, 8));
         n_bases = o[1] - o[0];
-        if (p->seq_mode == 2 && d_offs2) { STCHK(d2h(c, &o[0], d_offs2, 8)); STCHK(d2h(c, &o[1], d_offs2 + n_reads, 8)); n_bases += o[1] - o[0]; }
-        if (n_bases_exact) *n_bases_exact = n_bases;
+        if (p->seq_mode == 2 && rd.d_offs2) { STCHK(d2h(c, &o[0], rd.d_offs2, 8)); STCHK(d2h(c, &o[1], rd.d_offs2 + n_reads, 8)); n_bases += o[1] - o[0]; }
     }
     if (single_pass && n_bases) {
-        /* six frames x L/3 windows bound the output by 2 metamers per base; syncmer selection keeps about half of them:
-         * size the buffer from the previous batch's yield and fall back to the bound if that was too optimistic */
+        /* the buffer from the previous batch's yield (extract_cap_guess); the bound if that was too optimistic */
         const uint64_t bound = extract_bound(n_bases, grid);
         uint64_t cap = extract_cap_guess(c, p, n_bases, grid);
-        cap = std::max<uint64_t>(cap, std::min<uint64_t>(bound, c->bufs["kmersA"].cap / sizeof(mtb_kmer)));
+        cap = std::max<uint64_t>(cap, std::min<uint64_t>(bound, buf_cap(c, "kmersA") / sizeof(mtb_kmer)));
         for (int attempt = 0; attempt < 2; attempt++) {
             mtb_kmer *d_k; uint16_t *d_dig = nullptr;
             STCHK(ensure(c, "kmersA", cap, &d_k));
-            if (dig) { STCHK(ensure(c, "digA", cap + 8, &d_dig)); *dig = d_dig; }      /* (+8: the bucket-local histograms read whole 16-byte chunks) */
-            HIPCHK(hipMemsetAsync(c->d_xscal, 0, 64, c->stream));
-            if (d_off) HIPCHK(hipMemsetAsync(d_off, 0, n_reads, c->stream));
+            if (opt.want_digits) { STCHK(ensure(c, "digA", cap + 8, &d_dig)); ex->d_dig = d_dig; }      /* (+8: the bucket-local histograms read whole 16-byte chunks) */
+            HIPCHK(scal_clear(c, SC_EXTRACT, 8));
+            if (opt.d_off_reads) HIPCHK(hipMemsetAsync(opt.d_off_reads, 0, n_reads, c->stream));
             { KTimer kt(c, MTB_K_EXTRACT_EMIT);
-            hipLaunchKernelGGL((k_extract<2>), dim3(grid), dim3(64), 0, c->stream, a, c->d_tabs, d_counts, (const uint64_t *)nullptr,
-                               d_k, d_qlen, d_qlen2, (uint32_t *)(c->d_scal + 4), (unsigned long long *)c->d_xscal, cap, d_dig, d_off); }
+            hipLaunchKernelGGL((k_extract<2>), dim3(grid), dim3(64), 0, c->stream, a, c->d_tabs, opt.d_counts, (const uint64_t *)nullptr,
+                               d_k, d_qlen, d_qlen2, scal<uint32_t>(c, SC_MAX_LEN), scal<unsigned long long>(c, SC_EXTRACT), cap, d_dig, opt.d_off_reads); }
             HIPCHK(hipGetLastError());
-            uint64_t sc[8];
-            STCHK(d2h(c, sc, c->d_xscal, 64));             /* records allocated (incl. blank tails), overflow, real metamers, most metamers of a read; marked-read statistics */
-            if (off_stats) { off_stats[0] = sc[4]; off_stats[1] = sc[5]; off_stats[2] = sc[6]; }
-            if (max_len) { uint64_t ml = 0; STCHK(d2h(c, &ml, c->d_scal + 4, 8)); *max_len = (uint32_t)ml; }
-            if (sc[1] == 0) {
-                if (sc[0] >= (1ull << 32)) return fail(MTB_ERR_ARG, "more than 2^32-1 query metamers in one batch; split the batch");
-                c->extract_yield = (double)sc[0] / (double)n_bases;
-                *out = d_k; *count = sc[0];
-                if (real_count) *real_count = sc[2];
-                if (max_q) *max_q = (uint32_t)sc[3];
+            ExtractCounters sc;
+            STCHK(d2h(c, &sc, scal<uint64_t>(c, SC_EXTRACT), sizeof(sc)));
+            ex->off_max_q = sc.off_max_q; ex->off_reads = sc.off_reads; ex->off_max_len = sc.off_max_len;
+            if (opt.want_max_len) { uint64_t ml = 0; STCHK(d2h(c, &ml, scal<uint64_t>(c, SC_MAX_LEN), 8)); ex->max_len = (uint32_t)ml; }
+            if (sc.overflow == 0) {
+                if (sc.records >= (1ull << 32)) return fail(MTB_ERR_ARG, "more than 2^32-1 query metamers in one batch; split the batch");
+                c->extract_yield = (double)sc.records / (double)n_bases;
+                ex->d_k = d_k; ex->nk = sc.records; ex->nk_real = sc.real; ex->max_q = (uint32_t)sc.max_q;
                 return MTB_OK;
             }
             if (cap >= bound) return fail(MTB_ERR_DEVICE, "extract: output bound exceeded");
@@ -566,16 +592,15 @@ static mtb_status dev_extract(mtb_ctx *c, const mtb_params *p, const char *d_bas
         }
     }
     uint32_t *d_cnt; uint64_t *d_koff; uint64_t *d_ws;
-    STCHK(ensure(c, "counts", n_reads, &d_cnt));
-    STCHK(ensure(c, "koff", n_reads + 1, &d_koff));
+    STCHK(ensure(c, "counts", n_reads, &d_cnt)); STCHK(ensure(c, "koff", n_reads + 1, &d_koff));
     STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws));
     { KTimer kt(c, MTB_K_EXTRACT_COUNT);
     hipLaunchKernelGGL((k_extract<0>), dim3(grid), dim3(64), 0, c->stream, a, c->d_tabs, d_cnt, (const uint64_t *)nullptr,
-                       (mtb_kmer *)nullptr, d_qlen, d_qlen2, (uint32_t *)(c->d_scal + 4), (unsigned long long *)nullptr, (uint64_t)0); }
+                       (mtb_kmer *)nullptr, d_qlen, d_qlen2, scal<uint32_t>(c, SC_MAX_LEN), (unsigned long long *)nullptr, (uint64_t)0); }
     { KTimer kt(c, MTB_K_SCAN); scan_launch<uint32_t, uint64_t, false>(c->stream, d_cnt, n_reads, true, d_koff, d_ws); }
     uint64_t total = 0;
     STCHK(d2h(c, &total, d_koff + n_reads, 8));
-    if (max_len) { uint64_t ml = 0; STCHK(d2h(c, &ml, c->d_scal + 4, 8)); *max_len = (uint32_t)ml; }
+    if (opt.want_max_len) { uint64_t ml = 0; STCHK(d2h(c, &ml, scal<uint64_t>(c, SC_MAX_LEN), 8)); ex->max_len = (uint32_t)ml; }
     if (total >= (1ull << 32)) return fail(MTB_ERR_ARG, "more than 2^32-1 query metamers in one batch; split the batch");
     mtb_kmer *d_k;
     STCHK(ensure(c, "kmersA", total, &d_k));
@@ -584,15 +609,14 @@ static mtb_status dev_extract(mtb_ctx *c, const mtb_params *p, const char *d_bas
                            (const uint64_t *)d_koff, d_k, (int32_t *)nullptr, (int32_t *)nullptr, (uint32_t *)nullptr,
                            (unsigned long long *)nullptr, (uint64_t)0); }
     HIPCHK(hipGetLastError());
-    *out = d_k; *count = total;
-    if (real_count) *real_count = total;
+    ex->d_k = d_k; ex->nk = ex->nk_real = total;
     return MTB_OK;
 }
 
 /* first_bit >= 0: binary LSD passes over bits [first_bit, 64).  first_bit == MTB_SORT_AA6 (kmer_format 2): three
  * passes on amino-acid letter pairs = order by bits [34, 64) (kernels_sort.h). */
 #define MTB_SORT_AA6 (-6)
-static mtb_status dev_sort(mtb_ctx *c, mtb_kmer *d_a, uint64_t n, int first_bit, mtb_kmer **sorted, uint16_t *d_dig = nullptr, int aa_first_shift = 34) {
+static mtb_status dev_sort(mtb_ctx *c, mtb_kmer *d_a, uint64_t n, int first_bit, mtb_kmer **sorted, uint16_t *d_dig, int aa_first_shift) {
     *sorted = d_a;
     if (n == 0) return MTB_OK;
     const bool aa = first_bit == MTB_SORT_AA6;
@@ -740,25 +764,26 @@ struct IndexUse {
     ~IndexUse() { release(); }
 };
 
-/* join into d_out (cap entries); *count = matches found (may exceed cap -> MTB_ERR_CAPACITY).
+struct MatchList { mtb_match *d_out = nullptr; uint64_t cap = 0; uint32_t *d_read_cnt = nullptr; };     /* the join's dense output: cap records, optionally the matches per read; MatchList() = none (slot segments) */
+/* join into `list`; *count = matches found (may exceed list.cap -> MTB_ERR_CAPACITY).
  * With `seg` (per-read slot segments, k_join<SEG>) matches go to seg->seg and the overflow list instead; *count is then
- * the number of overflow entries needed and MTB_ERR_CAPACITY refers to the overflow list.                     */
-static mtb_status dev_join(mtb_ctx *c, mtb_index *ix, const mtb_kmer *d_q, uint64_t n, mtb_match *d_out, uint64_t cap,
-                           uint32_t *d_read_cnt, uint64_t *count, const JoinSegArgs *seg = nullptr, int sort_low_bits = 32) {
+ * the number of overflow entries needed and MTB_ERR_CAPACITY refers to the overflow list.  sort_low_bits: the bits the queries are NOT sorted on. */
+static mtb_status dev_join(mtb_ctx *c, mtb_index *ix, const mtb_kmer *d_q, uint64_t n, const MatchList &list, uint64_t *count, const JoinSegArgs *seg, int sort_low_bits) {
+    mtb_match *const d_out = list.d_out; const uint64_t cap = list.cap; uint32_t *const d_read_cnt = list.d_read_cnt;
     *count = 0;
     if (n == 0) return MTB_OK;
-    HIPCHK(hipMemsetAsync(c->d_scal, 0, 16, c->stream));
+    HIPCHK(scal_clear(c, SC_JOIN_COUNT, 2));
     uint32_t grid = (uint32_t)((n + MTB_JOIN_QPB - 1) / MTB_JOIN_QPB);
     uint64_t *d_bounds;
     STCHK(ensure(c, "jbounds", 2ull * grid, &d_bounds));
     uint64_t limit = ix->T ? ix->T - (ix->match_last ? 0 : 1) : 0;          /* the last entry of the (whole) index is never a candidate */
     IndexUse use;                     /* released after the stream sync below (the d2h of the counters) */
-    uint32_t win_tiles = 0;           /* the window variant ran: tiles launched (their statistics sit in d_scal[16..17]) */
+    uint32_t win_tiles = 0;           /* the window variant ran: tiles launched (their statistics sit in SC_WIN_STATS) */
     const bool striped = seg && ix->d_dir && !seg->list && !seg->dense_ovf;       /* the slot modes of the directory join: striped overflow list */
     if (seg && ix->d_dir) {
         STCHK(use.acquire(ix, true));
         KTimer kt(c, MTB_K_JOIN);
-        JoinSegArgs sa = *seg; sa.ovf_counter = (unsigned long long *)c->d_scal; sa.coop_min = c->opt.join_coop_min > 0 ? (uint32_t)c->opt.join_coop_min : (uint32_t)MTB_JOIN_COOP_MIN;
+        JoinSegArgs sa = *seg; sa.ovf_counter = scal<unsigned long long>(c, SC_JOIN_COUNT); sa.coop_min = c->opt.join_coop_min > 0 ? (uint32_t)c->opt.join_coop_min : (uint32_t)MTB_JOIN_COOP_MIN;
         if (striped) {
             HIPCHK(hipMemsetAsync(c->d_ovfctr, 0, MTB_OVF_STRIPES * 64, c->stream));
             sa.ovf_counter = c->d_ovfctr; sa.ovf_stripes = MTB_OVF_STRIPES; sa.ovf_region = sa.ovf_cap / MTB_OVF_STRIPES;
@@ -766,8 +791,8 @@ static mtb_status dev_join(mtb_ctx *c, mtb_index *ix, const mtb_kmer *d_q, uint6
         }
         const uint32_t g2 = (uint32_t)((n + 256 * MTB_JOIN_DIR_QPT - 1) / (256 * MTB_JOIN_DIR_QPT));
         if (sa.list) {      /* owner side of the partitioned index: a dense list of Match records */
-            if (state_owner(ix)->packed) hipLaunchKernelGGL((k_join_dir<true, 2>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, (uint32_t *)(c->d_scal + 1));
-            else hipLaunchKernelGGL((k_join_dir<false, 2>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, (uint32_t *)(c->d_scal + 1));
+            if (state_owner(ix)->packed) hipLaunchKernelGGL((k_join_dir<true, 2>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, scal<uint32_t>(c, SC_JOIN_OVERFLOW));
+            else hipLaunchKernelGGL((k_join_dir<false, 2>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, scal<uint32_t>(c, SC_JOIN_OVERFLOW));
         } else
         if (sa.rb) {        /* long reads: per-read slot ranges */
             if (state_owner(ix)->packed) {
@@ -784,20 +809,20 @@ static mtb_status dev_join(mtb_ctx *c, mtb_index *ix, const mtb_kmer *d_q, uint6
                     const uint32_t n_tiles = (uint32_t)((n + qt - 1) / qt);
                     mtb_tile_win *d_tw;
                     STCHK(ensure(c, "jtilewin", (size_t)n_tiles, &d_tw));
-                    HIPCHK(hipMemsetAsync(c->d_scal + 16, 0, 16, c->stream));
-                    hipLaunchKernelGGL(k_join_tile_win, dim3((n_tiles + 255) / 256), dim3(256), 0, c->stream, d_q, n, qt, dir_view(ix), limit, sort_low_bits, d_tw, n_tiles, (unsigned long long *)(c->d_scal + 16));
+                    HIPCHK(scal_clear(c, SC_WIN_STATS, 2));
+                    hipLaunchKernelGGL(k_join_tile_win, dim3((n_tiles + 255) / 256), dim3(256), 0, c->stream, d_q, n, qt, dir_view(ix), limit, sort_low_bits, d_tw, n_tiles, scal<unsigned long long>(c, SC_WIN_STATS));
                     hipLaunchKernelGGL((k_join_dir<true, 1, 1, MTB_JOIN_WIN_WAVES, true>), dim3(n_tiles), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa,
-                                       (uint32_t *)(c->d_scal + 1), qt, (const mtb_tile_win *)d_tw, (unsigned long long *)(c->d_scal + 16));
+                                       scal<uint32_t>(c, SC_JOIN_OVERFLOW), qt, (const mtb_tile_win *)d_tw, scal<unsigned long long>(c, SC_WIN_STATS));
                     win_tiles = n_tiles; c->stats.join_variant = MTB_JOIN_WINDOW;
                 } else
-                if (c->opt.join_variant != 0x25) hipLaunchKernelGGL((k_join_dir<true, 1, 1, 6>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, (uint32_t *)(c->d_scal + 1));
-                else hipLaunchKernelGGL((k_join_dir<true, 1, MTB_JOIN_DIR_QPT, 5>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, (uint32_t *)(c->d_scal + 1));
+                if (c->opt.join_variant != 0x25) hipLaunchKernelGGL((k_join_dir<true, 1, 1, 6>), dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, scal<uint32_t>(c, SC_JOIN_OVERFLOW));
+                else hipLaunchKernelGGL((k_join_dir<true, 1, MTB_JOIN_DIR_QPT, 5>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, scal<uint32_t>(c, SC_JOIN_OVERFLOW));
             }
-            else hipLaunchKernelGGL((k_join_dir<false, 1>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, (uint32_t *)(c->d_scal + 1));
+            else hipLaunchKernelGGL((k_join_dir<false, 1>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, scal<uint32_t>(c, SC_JOIN_OVERFLOW));
         } else
         if (state_owner(ix)->packed) {
             /* the product instantiation, or one of its A/B variants (queries per thread x waves per SIMD) */
-#define MTB_LAUNCH_JV(QV, WV) hipLaunchKernelGGL((k_join_dir<true, 0, QV, WV>), dim3((uint32_t)((n + 256 * QV - 1) / (256 * QV))), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, (uint32_t *)(c->d_scal + 1))
+#define MTB_LAUNCH_JV(QV, WV) hipLaunchKernelGGL((k_join_dir<true, 0, QV, WV>), dim3((uint32_t)((n + 256 * QV - 1) / (256 * QV))), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, scal<uint32_t>(c, SC_JOIN_OVERFLOW))
             /* Three exact instantiations of the short-read join on packed words (kernels_dir.h): sector-random lookups with one query per thread at 6 waves
              * per SIMD (q1w6) or two at 5 (q2w5), and the LDS window.  The window needs a batch dense enough that a tile of sorted queries addresses a
              * span of the target array that fits LDS -- a query owns T / n targets on average; qt queries per workgroup so that the expected window is
@@ -865,12 +890,12 @@ static mtb_status dev_join(mtb_ctx *c, mtb_index *ix, const mtb_kmer *d_q, uint6
                 mtb_tile_win *d_tw;
                 const bool sorted_ok = ix->params.kmer_format == 2 ? sort_low_bits == 34 : (sort_low_bits >= 24 && sort_low_bits <= 32);
                 STCHK(ensure(c, "jtilewin", (size_t)n_tiles, &d_tw));
-                HIPCHK(hipMemsetAsync(c->d_scal + 16, 0, 16, c->stream));
+                HIPCHK(scal_clear(c, SC_WIN_STATS, 2));
                 if (sorted_ok) hipLaunchKernelGGL(k_join_tile_win, dim3((n_tiles + 255) / 256), dim3(256), 0, c->stream, d_q, n, qt, dir_view(ix), limit, sort_low_bits, d_tw, n_tiles,
-                                                  (unsigned long long *)(c->d_scal + 16));
+                                                  scal<unsigned long long>(c, SC_WIN_STATS));
                 else HIPCHK(hipMemsetAsync(d_tw, 0, (size_t)n_tiles * sizeof(mtb_tile_win), c->stream));
 #define MTB_LAUNCH_JW(WV) hipLaunchKernelGGL((k_join_dir<true, 0, 1, WV, true>), dim3(n_tiles), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), \
-                                   (const mtb_tables *)c->d_tabs, sa, (uint32_t *)(c->d_scal + 1), qt, (const mtb_tile_win *)d_tw, (unsigned long long *)(c->d_scal + 16))
+                                   (const mtb_tables *)c->d_tabs, sa, scal<uint32_t>(c, SC_JOIN_OVERFLOW), qt, (const mtb_tile_win *)d_tw, scal<unsigned long long>(c, SC_WIN_STATS))
                 switch (win_waves) {
                 case 5: MTB_LAUNCH_JW(5); break;
                 case 6: MTB_LAUNCH_JW(6); break;
@@ -889,28 +914,28 @@ static mtb_status dev_join(mtb_ctx *c, mtb_index *ix, const mtb_kmer *d_q, uint6
 #undef MTB_LAUNCH_JV
             if (timing_this) HIPCHK(hipEventRecord(jt->e1, c->stream));
         }
-        else hipLaunchKernelGGL((k_join_dir<false>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, (uint32_t *)(c->d_scal + 1));
+        else hipLaunchKernelGGL((k_join_dir<false>), dim3(g2), dim3(256), 0, c->stream, d_q, n, index_view(ix), limit, dir_view(ix), (const mtb_tables *)c->d_tabs, sa, scal<uint32_t>(c, SC_JOIN_OVERFLOW));
     } else
     { STCHK(use.acquire(ix, false));
     KTimer kt(c, MTB_K_JOIN);
     hipLaunchKernelGGL(k_join_bounds, dim3((grid + 255) / 256), dim3(256), 0, c->stream, d_q, n, (const uint64_t *)ix->d_values, limit,
                        (uint64_t)grid, d_bounds, sort_low_bits);
     if (seg) {
-        JoinSegArgs sa = *seg; sa.ovf_counter = (unsigned long long *)c->d_scal;
+        JoinSegArgs sa = *seg; sa.ovf_counter = scal<unsigned long long>(c, SC_JOIN_COUNT);
         hipLaunchKernelGGL((k_join<true>), dim3(grid), dim3(256), 0, c->stream, d_q, n, index_view(ix), (const mtb_tables *)c->d_tabs,
                            (const uint64_t *)d_bounds, (mtb_match *)nullptr, (uint64_t)0, (unsigned long long *)nullptr, (uint32_t *)nullptr,
-                           (uint32_t *)(c->d_scal + 1), sa);
+                           scal<uint32_t>(c, SC_JOIN_OVERFLOW), sa);
     } else {
         JoinSegArgs sa; memset(&sa, 0, sizeof(sa));
         hipLaunchKernelGGL((k_join<false>), dim3(grid), dim3(256), 0, c->stream, d_q, n, index_view(ix), (const mtb_tables *)c->d_tabs,
-                           (const uint64_t *)d_bounds, d_out, cap, (unsigned long long *)c->d_scal, d_read_cnt, (uint32_t *)(c->d_scal + 1), sa);
+                           (const uint64_t *)d_bounds, d_out, cap, scal<unsigned long long>(c, SC_JOIN_COUNT), d_read_cnt, scal<uint32_t>(c, SC_JOIN_OVERFLOW), sa);
     } }
     HIPCHK(hipGetLastError());
     uint64_t sc[2];
-    STCHK(d2h(c, sc, c->d_scal, 16));
+    STCHK(d2h(c, sc, scal<uint64_t>(c, SC_JOIN_COUNT), 16));
     if (win_tiles) {
         uint64_t ws[2];
-        STCHK(d2h(c, ws, c->d_scal + 16, 16));
+        STCHK(d2h(c, ws, scal<uint64_t>(c, SC_WIN_STATS), 16));
         c->stats.join_tiles = win_tiles; c->stats.join_tiles_windowed = (uint32_t)ws[0]; c->stats.join_tiles_outside = (uint32_t)ws[1];
     }
     if (striped) {
@@ -956,15 +981,15 @@ static mtb_status dev_regroup(mtb_ctx *c, const mtb_match *d_in, uint64_t m, uin
 static mtb_status dev_segsort(mtb_ctx *c, mtb_match *d_m, const uint64_t *d_seg, uint64_t n_reads, uint32_t *max_seg) {
     uint32_t *d_large;
     STCHK(ensure(c, "large", n_reads, &d_large));
-    HIPCHK(hipMemsetAsync(c->d_scal + 2, 0, 16, c->stream));
+    HIPCHK(scal_clear(c, SC_N_LARGE, 2));
     uint32_t grid = (uint32_t)std::min<uint64_t>(n_reads, 256ull * 40);
     { KTimer kt(c, MTB_K_SEGSORT);
-    hipLaunchKernelGGL(k_segsort_small, dim3(grid), dim3(64), 0, c->stream, d_m, d_seg, n_reads, d_large, (uint32_t *)(c->d_scal + 2),
-                       (uint32_t *)(c->d_scal + 3)); }
+    hipLaunchKernelGGL(k_segsort_small, dim3(grid), dim3(64), 0, c->stream, d_m, d_seg, n_reads, d_large, scal<uint32_t>(c, SC_N_LARGE),
+                       scal<uint32_t>(c, SC_MAX_SEG)); }
     hipLaunchKernelGGL((k_segsort_large<mtb_match>), dim3(1024), dim3(256), 0, c->stream, d_m, d_seg, (const uint32_t *)d_large,
-                       (const uint32_t *)(c->d_scal + 2));
+                       scal<const uint32_t>(c, SC_N_LARGE));
     HIPCHK(hipGetLastError());
-    if (max_seg) { uint64_t sc[2]; STCHK(d2h(c, sc, c->d_scal + 2, 16)); *max_seg = (uint32_t)sc[1]; }
+    if (max_seg) { uint64_t sc[2]; STCHK(d2h(c, sc, scal<uint64_t>(c, SC_N_LARGE), 16)); *max_seg = (uint32_t)sc[1]; }
     return MTB_OK;
 }
 
@@ -981,6 +1006,7 @@ struct ScoreSrc {
     int seg_by_list = 0;
     bool sort = false;                    /* segments arrive unordered: rank sort in the kernel */
     uint32_t max_seg = 0;                 /* largest segment this launch can meet */
+    uint32_t max_len_deferred = 0;        /* the launch over the reads this one defers may meet longer reads than lens.max_len (reads routed around the slot segments) */
     uint32_t grid = 0;                    /* 0 = default */
     const uint8_t *only_flagged = nullptr; /* slot mode after k_score_fast: score only the reads it flagged */
     const uint32_t *seg_cnt = nullptr;     /* slab launches: matches per read when the segment does not fill [seg[r], seg[r + 1]) */
@@ -990,32 +1016,29 @@ struct ScoreSrc {
 /* d_results/d_tc_* are device outputs; *n_tc = sum of per-read bounds.  `second` (optional) runs after the launch
  * over `first`, may build a source for the reads that launch deferred (large-segment path) and returns true to
  * have it launched with the same per-read taxcnt slots. */
-struct ScoreLaunch {                      /* what dev_score has set up by the time `second` runs: enough to launch a scorer of its own */
-    const uint64_t *d_tcoff; bool key64; mtb_score_params sp;
-    const int32_t *d_qlen, *d_qlen2; mtb_result *d_res; int32_t *d_tc_tax; uint32_t *d_tc_cnt; uint64_t tc_cap, tc_base;
-};
+struct ScoreLaunch { const uint64_t *d_tcoff; bool key64; mtb_score_params sp; ReadLens lens; ResultSink out; };     /* what dev_score has set up by the time `second` runs: enough to launch a scorer of its own */
 typedef std::function<mtb_status(ScoreSrc *, bool *, const ScoreLaunch &)> ScoreSecond;
-static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const int32_t *d_qlen, const int32_t *d_qlen2,
-                            uint32_t max_len, mtb_result *d_res, int32_t *d_tc_tax, uint32_t *d_tc_cnt, uint64_t tc_cap, uint64_t *n_tc,
-                            uint64_t tc_base, const ScoreSrc &first, const ScoreSecond *second,
-                            uint32_t max_len_second = 0 /* the deferred reads' launch may meet longer reads than the first one (reads routed around the slot segments) */) {
-    mtb_score_params sp; mtb_make_score_params(p, &sp);
-    uint32_t *d_bound; uint64_t *d_tcoff; uint64_t *d_ws;
-    STCHK(ensure(c, "bound", n_reads, &d_bound));
-    STCHK(ensure(c, "tcoff", n_reads + 1, &d_tcoff));
-    STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws));
-    hipLaunchKernelGGL(k_taxcnt_bound, dim3((uint32_t)((n_reads + 63) / 64)), dim3(64), 0, c->stream, first.seg, first.cursor ? first.cursor : (const uint32_t *)first.bound_by_buckets,
-                       d_qlen, d_qlen2, n_reads, sp.dna_shift, d_bound);
+/* per-read bounds of the taxcnt slots (k_taxcnt_bound over seg / cnt) -> d_tcoff (n_reads + 1); *n_tc = their sum, checked against the sink */
+static mtb_status taxcnt_layout(mtb_ctx *c, uint64_t n_reads, const uint64_t *d_seg, const uint32_t *d_cnt, const ReadLens &lens, const ResultSink &out, int dna_shift, uint64_t *d_tcoff, uint64_t *n_tc) {
+    uint32_t *d_bound; uint64_t *d_ws;
+    STCHK(ensure(c, "bound", n_reads, &d_bound)); STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws));
+    hipLaunchKernelGGL(k_taxcnt_bound, dim3((uint32_t)((n_reads + 63) / 64)), dim3(64), 0, c->stream, d_seg, d_cnt, lens.d_ql, lens.d_ql2, n_reads, dna_shift, d_bound);
     { KTimer kt(c, MTB_K_SCAN); scan_launch<uint32_t, uint64_t, false>(c->stream, d_bound, n_reads, true, d_tcoff, d_ws); }
-    uint64_t tot = 0;
-    STCHK(d2h(c, &tot, d_tcoff + n_reads, 8));
-    *n_tc = tot;
-    if (tot > tc_cap) return fail(MTB_ERR_CAPACITY, "taxcnt buffers too small");
-    if (tc_base + tot >= (1ull << 32)) return fail(MTB_ERR_ARG, "more than 2^32-1 taxcnt slots in one batch (mtb_result.taxcnt_off is 32 bits); split the batch");
+    STCHK(d2h(c, n_tc, d_tcoff + n_reads, 8));
+    if (*n_tc > out.tc_cap) return fail(MTB_ERR_CAPACITY, "taxcnt buffers too small");
+    if (out.tc_base + *n_tc >= (1ull << 32)) return fail(MTB_ERR_ARG, "more than 2^32-1 taxcnt slots in one batch (mtb_result.taxcnt_off is 32 bits); split the batch");
+    return MTB_OK;
+}
+static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const ReadLens &lens, const ResultSink &out, uint64_t *n_tc,
+                            const ScoreSrc &first, const ScoreSecond *second) {
+    mtb_score_params sp; mtb_make_score_params(p, &sp);
+    uint64_t *d_tcoff;
+    STCHK(ensure(c, "tcoff", n_reads + 1, &d_tcoff));
+    STCHK(taxcnt_layout(c, n_reads, first.seg, first.cursor ? first.cursor : (const uint32_t *)first.bound_by_buckets, lens, out, sp.dna_shift, d_tcoff, n_tc));
     /* single-word sort key when taxids < 2^22 and positions < 2^11 (hamming of a match is <= 7) */
-    const bool key64 = ix->tax.max_id < (1 << 22) && max_len + 3 < (1u << 11);
-    const uint32_t max_nb_first = (uint32_t)mtb_num_buckets((int32_t)max_len, sp.dna_shift);
-    const uint32_t max_nb_second = (uint32_t)mtb_num_buckets((int32_t)std::max(max_len, max_len_second), sp.dna_shift);
+    const bool key64 = ix->tax.max_id < (1 << 22) && lens.max_len + 3 < (1u << 11);
+    const uint32_t max_nb_first = (uint32_t)mtb_num_buckets((int32_t)lens.max_len, sp.dna_shift);
+    const uint32_t max_nb_second = (uint32_t)mtb_num_buckets((int32_t)std::max(lens.max_len, first.max_len_deferred), sp.dna_shift);
     if (max_nb_second > 65535u) return fail(MTB_ERR_ARG, "read too long for mtb_result.n_taxcnt (16 bits): more than 65535 position buckets");
     ScoreSrc second_src;
     for (int pass = 0; pass < 2; pass++) {
@@ -1024,8 +1047,7 @@ static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint
         if (pass == 1) {
             if (!second) break;
             bool go = false;
-            ScoreLaunch SL; SL.d_tcoff = d_tcoff; SL.key64 = key64; SL.sp = sp; SL.d_qlen = d_qlen; SL.d_qlen2 = d_qlen2; SL.d_res = d_res;
-            SL.d_tc_tax = d_tc_tax; SL.d_tc_cnt = d_tc_cnt; SL.tc_cap = tc_cap; SL.tc_base = tc_base;
+            const ScoreLaunch SL{d_tcoff, key64, sp, lens, out};
             STCHK((*second)(&second_src, &go, SL));
             if (!go) break;
             S = &second_src;
@@ -1043,13 +1065,13 @@ static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint
         if (dynamic) grid = std::min<uint32_t>(grid, 256u * 14u);
         if (slab_bytes) {
             while ((uint64_t)grid * slab_bytes > (MTB_SLAB_POOL_MAX) && grid > 64) grid /= 2;     /* keep the slab pool bounded (a halved grid halves the waves that hide the slab's HBM latency) */
-            STCHK(ensure(c, "slabs", (size_t)grid * slab_bytes, &d_slabs));
+            STCHK(ensure(c, "slabs", (size_t)grid * slab_bytes, &d_slabs, BUF_FIXED));
         }
         unsigned long long *d_work = nullptr;
-        if (dynamic) { d_work = (unsigned long long *)(c->d_xscal + 4 + pass); HIPCHK(hipMemsetAsync(d_work, 0, 8, c->stream)); }
-#define MTB_LAUNCH_SCORE(SRT, K, CAPV, DYNV, SLOTV) hipLaunchKernelGGL((k_score<SRT, K, mtb_match, CAPV, DYNV, SLOTV>), dim3(grid), dim3(64), 0, c->stream, S->m, S->seg, n_reads, d_qlen, \
-        d_qlen2, tax_view(ix), sp, (const uint64_t *)d_tcoff, d_res, d_tc_tax, d_tc_cnt, tc_cap, d_slabs, slab_bytes, slab_n, slab_nb, (mtb_match *)nullptr,  \
-        tc_base, S->list, S->n_list, S->cursor, S->stride, S->seg_by_list, S->direct, S->epoch, S->big_list, S->n_big, S->cnt_out, d_work, S->only_flagged, S->seg_cnt)
+        if (dynamic) { d_work = scal<unsigned long long>(c, SC_SCORE_WORK) + pass; HIPCHK(hipMemsetAsync(d_work, 0, 8, c->stream)); }
+#define MTB_LAUNCH_SCORE(SRT, K, CAPV, DYNV, SLOTV) hipLaunchKernelGGL((k_score<SRT, K, mtb_match, CAPV, DYNV, SLOTV>), dim3(grid), dim3(64), 0, c->stream, S->m, S->seg, n_reads, lens.d_ql, \
+        lens.d_ql2, tax_view(ix), sp, (const uint64_t *)d_tcoff, out.d_res, out.d_tc_tax, out.d_tc_cnt, out.tc_cap, d_slabs, slab_bytes, slab_n, slab_nb, (mtb_match *)nullptr,  \
+        out.tc_base, S->list, S->n_list, S->cursor, S->stride, S->seg_by_list, S->direct, S->epoch, S->big_list, S->n_big, S->cnt_out, d_work, S->only_flagged, S->seg_cnt)
         ScoreSrc S_rest;
         const bool pairs = p->seq_mode == 2;
         if (S->cursor && pass == 0 && key64 && S->stride <= 384u && !c->opt.no_fast_scorer && !(pairs && c->opt.no_fast_pairs)) {
@@ -1059,14 +1081,14 @@ static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint
             uint8_t *d_slow;
             STCHK(ensure(c, "slowflag", n_reads, &d_slow));
             HIPCHK(hipMemsetAsync(d_slow, 0, n_reads, c->stream));
-            HIPCHK(hipMemsetAsync(c->d_scal + 6, 0, 8, c->stream));
-#define MTB_LAUNCH_FAST(...) hipLaunchKernelGGL((k_score_fast<__VA_ARGS__>), dim3(grid), dim3(64), 0, c->stream, (const mtb_slot16 *)S->m, n_reads, d_qlen, d_qlen2, tax_view(ix), sp, \
-            (const uint64_t *)d_tcoff, d_res, d_tc_tax, d_tc_cnt, tc_cap, tc_base, S->cursor, S->stride, S->direct, S->epoch, d_slow, S->cnt_out)
+            HIPCHK(scal_clear(c, SC_N_GENERIC));
+#define MTB_LAUNCH_FAST(...) hipLaunchKernelGGL((k_score_fast<__VA_ARGS__>), dim3(grid), dim3(64), 0, c->stream, (const mtb_slot16 *)S->m, n_reads, lens.d_ql, lens.d_ql2, tax_view(ix), sp, \
+            (const uint64_t *)d_tcoff, out.d_res, out.d_tc_tax, out.d_tc_cnt, out.tc_cap, out.tc_base, S->cursor, S->stride, S->direct, S->epoch, d_slow, S->cnt_out)
             { KTimer ktf(c, MTB_K_SCORE_FAST);
               if (pairs) { if (S->stride <= 192) MTB_LAUNCH_FAST(3, 3, true); else if (S->stride <= 256) MTB_LAUNCH_FAST(4, 4, true); else MTB_LAUNCH_FAST(5, 6, true); }
               else if (S->stride <= 128) MTB_LAUNCH_FAST(2); else if (S->stride <= 192) MTB_LAUNCH_FAST(3); else if (S->stride <= 256) MTB_LAUNCH_FAST(4); else MTB_LAUNCH_FAST(5, 6, false); }
 #undef MTB_LAUNCH_FAST
-            hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_slow, n_reads, (unsigned long long *)(c->d_scal + 6));
+            hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_slow, n_reads, scal<unsigned long long>(c, SC_N_GENERIC));
             if (S->big_list && S->n_big) hipLaunchKernelGGL(k_list_flag2, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_slow, n_reads, S->big_list, S->n_big);
             c->fast_used = true;
             S_rest = *S; S_rest.only_flagged = d_slow;
@@ -1094,49 +1116,40 @@ static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint
     return MTB_OK;
 }
 
+struct LongSegs {                         /* the sorted exact segments k_score_long streams */
+    const mtb_match *d_m = nullptr; const uint64_t *d_seg = nullptr; uint32_t max_seg = 0;
+    const uint32_t *d_segcnt = nullptr, *d_list = nullptr; uint32_t n_list = 0;      /* matches per read when a segment does not fill [seg[r], seg[r + 1]) (slot ranges); only these reads: segments indexed by the list slot, taxcnt slots as laid out by a previous call */
+};
 /* Long reads (seq_mode 3): exact segments in compareMatches order -> k_score_long, one workgroup per read (kernels_score_long.h).
  * Reads it cannot take (LDS budgets) are flagged and scored by the generic slab launch of dev_score afterwards. */
-static mtb_status dev_score_long(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const int32_t *d_qlen, const int32_t *d_qlen2,
-                                 uint32_t max_len, mtb_result *d_res, int32_t *d_tc_tax, uint32_t *d_tc_cnt, uint64_t tc_cap, uint64_t *n_tc,
-                                 uint64_t tc_base, const mtb_match *d_m, const uint64_t *d_seg, uint32_t max_seg, const uint32_t *d_segcnt = nullptr,
-                                 const uint32_t *d_list = nullptr, uint32_t n_list = 0 /* only these reads; segments indexed by the list slot; taxcnt slots as laid out by a previous call */) {
+static mtb_status dev_score_long(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const ReadLens &lens, const ResultSink &out, uint64_t *n_tc, const LongSegs &sg) {
     mtb_score_params sp; mtb_make_score_params(p, &sp);
-    uint32_t *d_bound; uint64_t *d_tcoff; uint64_t *d_ws; uint8_t *d_todo;
-    STCHK(ensure(c, "bound", n_reads, &d_bound));
-    STCHK(ensure(c, "tcoff", n_reads + 1, &d_tcoff));
-    STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws));
-    STCHK(ensure(c, "slowflag", n_reads, &d_todo));
-    if (!d_list) {
+    uint64_t *d_tcoff; uint8_t *d_todo;
+    STCHK(ensure(c, "tcoff", n_reads + 1, &d_tcoff)); STCHK(ensure(c, "slowflag", n_reads, &d_todo));
+    if (!sg.d_list) {
         /* per-read taxcnt slots: one per position bucket (slot ranges: the match count is not known yet), else min(matches, buckets) */
-        hipLaunchKernelGGL(k_taxcnt_bound, dim3((uint32_t)((n_reads + 63) / 64)), dim3(64), 0, c->stream, d_seg, d_segcnt, d_qlen, d_qlen2,
-                           n_reads, sp.dna_shift, d_bound);
-        { KTimer kt(c, MTB_K_SCAN); scan_launch<uint32_t, uint64_t, false>(c->stream, d_bound, n_reads, true, d_tcoff, d_ws); }
-        uint64_t tot = 0;
-        STCHK(d2h(c, &tot, d_tcoff + n_reads, 8));
-        *n_tc = tot;
-        if (tot > tc_cap) return fail(MTB_ERR_CAPACITY, "taxcnt buffers too small");
-        if (tc_base + tot >= (1ull << 32)) return fail(MTB_ERR_ARG, "more than 2^32-1 taxcnt slots in one batch (mtb_result.taxcnt_off is 32 bits); split the batch");
-        const uint32_t max_nb = (uint32_t)mtb_num_buckets((int32_t)max_len, sp.dna_shift);
+        STCHK(taxcnt_layout(c, n_reads, sg.d_seg, sg.d_segcnt, lens, out, sp.dna_shift, d_tcoff, n_tc));
+        const uint32_t max_nb = (uint32_t)mtb_num_buckets((int32_t)lens.max_len, sp.dna_shift);
         if (max_nb > 65535u) return fail(MTB_ERR_ARG, "read too long for mtb_result.n_taxcnt (16 bits): more than 65535 position buckets");
     }
     HIPCHK(hipMemsetAsync(d_todo, 0, n_reads, c->stream));
-    unsigned long long *d_work = (unsigned long long *)(c->d_xscal + 6);
+    unsigned long long *d_work = scal<unsigned long long>(c, SC_LONG_WORK);
     HIPCHK(hipMemsetAsync(d_work, 0, 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_scal + 6, 0, 8, c->stream));
+    HIPCHK(scal_clear(c, SC_LONG_N_SECOND));
     {   KTimer kt(c, MTB_K_SCORE_FAST);       /* booked with the register-resident scorer's id: the workgroup-per-read kernel of long reads */
         /* two launches (round 6): <.., 512 paths, 2048 position buckets> first -- 33 KB of LDS, four workgroups per CU; reads up to ~18 kb with up to 512 emitted
          * paths: nearly all -- then the full budgets (70 KB, two per CU) for the reads the first one flagged */
-        const uint64_t n_it = d_list ? n_list : n_reads;
-        hipLaunchKernelGGL((k_score_long<MTB_LONG_MAXBLK, MTB_LONG_MAXSP, 512, 2048>), dim3((uint32_t)std::min<uint64_t>(n_it, 256ull * 4)), dim3(MTB_LONG_NT), 0, c->stream, d_m, d_seg, n_reads, d_qlen, d_qlen2, tax_view(ix), sp, (const uint64_t *)d_tcoff,
-                           d_res, d_tc_tax, d_tc_cnt, tc_cap, tc_base, d_todo, d_work, d_segcnt, d_list, n_list, 0u);
-        hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_todo, n_reads, (unsigned long long *)(c->d_scal + 6));
+        const uint64_t n_it = sg.d_list ? sg.n_list : n_reads;
+        hipLaunchKernelGGL((k_score_long<MTB_LONG_MAXBLK, MTB_LONG_MAXSP, 512, 2048>), dim3((uint32_t)std::min<uint64_t>(n_it, 256ull * 4)), dim3(MTB_LONG_NT), 0, c->stream, sg.d_m, sg.d_seg, n_reads, lens.d_ql, lens.d_ql2, tax_view(ix), sp, (const uint64_t *)d_tcoff,
+                           out.d_res, out.d_tc_tax, out.d_tc_cnt, out.tc_cap, out.tc_base, d_todo, d_work, sg.d_segcnt, sg.d_list, sg.n_list, 0u);
+        hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_todo, n_reads, scal<unsigned long long>(c, SC_LONG_N_SECOND));
         uint64_t n_second = 0;
-        STCHK(d2h(c, &n_second, c->d_scal + 6, 8));
-        HIPCHK(hipMemsetAsync(c->d_scal + 6, 0, 8, c->stream));
+        STCHK(d2h(c, &n_second, scal<uint64_t>(c, SC_LONG_N_SECOND), 8));
+        HIPCHK(scal_clear(c, SC_N_GENERIC));
         if (n_second) {
             HIPCHK(hipMemsetAsync(d_work, 0, 8, c->stream));
-            hipLaunchKernelGGL((k_score_long<MTB_LONG_MAXBLK, MTB_LONG_MAXSP>), dim3((uint32_t)std::min<uint64_t>(n_it, 256ull * 2)), dim3(MTB_LONG_NT), 0, c->stream, d_m, d_seg, n_reads, d_qlen, d_qlen2, tax_view(ix), sp, (const uint64_t *)d_tcoff,
-                               d_res, d_tc_tax, d_tc_cnt, tc_cap, tc_base, d_todo, d_work, d_segcnt, d_list, n_list, 1u);
+            hipLaunchKernelGGL((k_score_long<MTB_LONG_MAXBLK, MTB_LONG_MAXSP>), dim3((uint32_t)std::min<uint64_t>(n_it, 256ull * 2)), dim3(MTB_LONG_NT), 0, c->stream, sg.d_m, sg.d_seg, n_reads, lens.d_ql, lens.d_ql2, tax_view(ix), sp, (const uint64_t *)d_tcoff,
+                               out.d_res, out.d_tc_tax, out.d_tc_cnt, out.tc_cap, out.tc_base, d_todo, d_work, sg.d_segcnt, sg.d_list, sg.n_list, 1u);
         }
 #ifdef MTB_LONG_PHASE_CYCLES
     {   /* profiling build: cycles of thread 0 per phase of k_score_long, summed over the workgroups (and reset) */
@@ -1146,26 +1159,31 @@ static mtb_status dev_score_long(mtb_ctx *c, mtb_index *ix, const mtb_params *p,
         HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(mtb_long_cycles), z, sizeof(z)));
         static const char *nm[10] = {"setup", "block list", "walk", "rank", "species ranges", "combination", "decision", "filter", "taxCnt gather", "descent + output + next read"};
         unsigned long long tot = 0; for (int k = 0; k < 10; k++) tot += h[k];
-        fprintf(stderr, "k_score_long phases (%llu reads):", (unsigned long long)(d_list ? n_list : n_reads));
+        fprintf(stderr, "k_score_long phases (%llu reads):", (unsigned long long)(sg.d_list ? sg.n_list : n_reads));
         for (int k = 0; k < 10; k++) fprintf(stderr, " %s %.1f %%;", nm[k], tot ? 100.0 * (double)h[k] / (double)tot : 0.0);
         fprintf(stderr, "\n");
     }
 #endif
     }
-    hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_todo, n_reads, (unsigned long long *)(c->d_scal + 6));
+    hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_todo, n_reads, scal<unsigned long long>(c, SC_N_GENERIC));
     HIPCHK(hipGetLastError());
     uint64_t n_left = 0;
-    STCHK(d2h(c, &n_left, c->d_scal + 6, 8));
-    c->fast_used = true;                      /* statistics: d_scal[6] = reads the generic kernel scores */
+    STCHK(d2h(c, &n_left, scal<uint64_t>(c, SC_N_GENERIC), 8));
+    c->fast_used = true;
     if (n_left == 0) return MTB_OK;
-    ScoreSrc a; a.m = d_m; a.seg = d_seg; a.sort = false; a.max_seg = std::max<uint32_t>(max_seg, MTB_SCORE_LDS + 1); a.only_flagged = d_todo; a.seg_cnt = d_segcnt;
-    a.bound_by_buckets = d_segcnt ? (const void *)d_segcnt : (const void *)d_list;      /* the same taxcnt layout as above */
+    ScoreSrc a; a.m = sg.d_m; a.seg = sg.d_seg; a.sort = false; a.max_seg = std::max<uint32_t>(sg.max_seg, MTB_SCORE_LDS + 1); a.only_flagged = d_todo; a.seg_cnt = sg.d_segcnt;
+    a.bound_by_buckets = sg.d_segcnt ? (const void *)sg.d_segcnt : (const void *)sg.d_list;      /* the same taxcnt layout as above */
     uint32_t *d_nl = nullptr;
-    if (d_list) { STCHK(ensure(c, "lnlist", 2, &d_nl)); STCHK(h2d(c, d_nl, &n_list, 4)); a.list = d_list; a.n_list = d_nl; a.seg_by_list = 1; }
+    if (sg.d_list) { STCHK(ensure(c, "lnlist", 2, &d_nl)); STCHK(h2d(c, d_nl, &sg.n_list, 4)); a.list = sg.d_list; a.n_list = d_nl; a.seg_by_list = 1; }
     uint64_t n_tc2 = 0;
-    STCHK(dev_score(c, ix, p, n_reads, d_qlen, d_qlen2, max_len, d_res, d_tc_tax, d_tc_cnt, tc_cap, &n_tc2, tc_base, a, nullptr));
-    HIPCHK(hipMemsetAsync(c->d_scal + 6, 0, 8, c->stream));         /* dev_score's statistics slot: put the count back */
-    hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_todo, n_reads, (unsigned long long *)(c->d_scal + 6));
+    STCHK(dev_score(c, ix, p, n_reads, lens, out, &n_tc2, a, /* nothing deferred */ nullptr));
+    HIPCHK(scal_clear(c, SC_N_GENERIC));         /* put the count back */
+    hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_todo, n_reads, scal<unsigned long long>(c, SC_N_GENERIC));
+    return MTB_OK;
+}
+/* Reads of the batch the generic kernel scored (statistics): `all` unless a listing scorer ran since the last call and left its count in SC_N_GENERIC. */
+static mtb_status take_generic_reads(mtb_ctx *c, uint64_t all, uint64_t *n) {
+    *n = all; if (c->fast_used) { STCHK(d2h(c, n, scal<uint64_t>(c, SC_N_GENERIC), 8)); *n &= 0xFFFFFFFFull; c->fast_used = false; }
     return MTB_OK;
 }
 
@@ -1176,10 +1194,10 @@ static mtb_status dev_score_long(mtb_ctx *c, mtb_index *ix, const mtb_params *p,
 static mtb_status count_reads(mtb_ctx *c, const mtb_match *d_in, uint64_t n, uint64_t n_reads, uint32_t *d_rc) {
     HIPCHK(hipMemsetAsync(d_rc, 0, n_reads * 4, c->stream));
     if (n == 0) return MTB_OK;
-    HIPCHK(hipMemsetAsync(c->d_scal + 1, 0, 8, c->stream));
-    hipLaunchKernelGGL(k_count_reads, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, n, d_rc, n_reads, (uint32_t *)(c->d_scal + 1));
+    HIPCHK(scal_clear(c, SC_BAD_SEQ));
+    hipLaunchKernelGGL(k_count_reads, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, c->stream, d_in, n, d_rc, n_reads, scal<uint32_t>(c, SC_BAD_SEQ));
     uint64_t bad = 0;
-    STCHK(d2h(c, &bad, c->d_scal + 1, 8));
+    STCHK(d2h(c, &bad, scal<uint64_t>(c, SC_BAD_SEQ), 8));
     if (bad) return fail(MTB_ERR_ARG, "match records with a sequenceID outside 1..n_reads");
     return MTB_OK;
 }
@@ -1226,7 +1244,7 @@ static mtb_status build_directory(mtb_ctx *c, mtb_index *ix) {
     size_t fr = 0, tot = 0;
     HIPCHK(hipMemGetInfo(&fr, &tot));
     if (((size_t)nbk + 1) * 4 + ((size_t)n_groups + 2) * 8 + (64u << 20) > fr) return MTB_OK;       /* no room: the bisection join still works */
-    uint32_t *d_flags = (uint32_t *)(c->d_scal + 6);
+    uint32_t *d_flags = scal<uint32_t>(c, SC_OPEN_FLAGS);
     HIPCHK(hipMalloc((void **)&ix->d_dir, ((size_t)nbk + 1) * 4));
     HIPCHK(hipMalloc((void **)&ix->d_dirbase, ((size_t)n_groups + 2) * 8));
     HIPCHK(hipMemsetAsync(d_flags, 0, 8, c->stream));
@@ -1373,8 +1391,8 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
     if (c->opt.open_chunk > 0) CH = std::max<uint64_t>(16, (uint64_t)c->opt.open_chunk);
     const int fmt = ix->params.kmer_format;
     const uint32_t nbk = want_dir ? mtb_pow21(L) : 0, n_groups = want_dir ? (nbk >> 16) + 1 : 0;
-    uint32_t *d_flags = (uint32_t *)(c->d_scal + 6);
-    uint64_t *d_carry = c->d_scal + 5;                      /* last flat value of the previous chunk */
+    uint32_t *d_flags = scal<uint32_t>(c, SC_OPEN_FLAGS);
+    uint64_t *d_carry = scal<uint64_t>(c, SC_OPEN_CARRY);                      /* last flat value of the previous chunk */
     if (want_dir) {
         HIPCHK(hipMalloc((void **)&ix->d_dir, ((size_t)nbk + 1) * 4));
         HIPCHK(hipMalloc((void **)&ix->d_dirbase, ((size_t)n_groups + 2) * 8));
@@ -1571,7 +1589,7 @@ static mtb_status open_impl(mtb_ctx *c, const char *dbdir, const char *taxonomy_
         const bool pack_guess = L == 7 && !P.drop_last && !c->opt.no_pack && (c->opt.open_packed >= 0 ? c->opt.open_packed != 0 : T >= (1ull << 28));
         const size_t need_dir = ((size_t)nbk + 1) * 4 + ((size_t)(nbk >> 16) + 3) * 8 + (T + 1) * 8 + (64u << 20);
         const size_t need_all = need_dir + (pack_guess ? 0 : (size_t)T * 4) + (std::min<uint64_t>(O.n16, 1ull << 27) * 12 + (64u << 20));
-        if (need_all > fr && held_bytes(c) > 0) fr = open_make_room(c);      /* a reservation made for the first batches must not cost the index its directory */
+        if (need_all > fr && held_bytes(c, BUF_FIXED) > 0) fr = open_make_room(c);      /* a reservation made for the first batches must not cost the index its directory */
         if (need_dir > fr) want_dir = false;        /* no room next to the values: the bisection join still works */
     }
     /* pack on load: big databases (>= 2^28 targets; MTB_OPEN_PACKED=1 / 0 forces it on toy databases / off) whose directory has depth 7
@@ -1583,11 +1601,11 @@ static mtb_status open_impl(mtb_ctx *c, const char *dbdir, const char *taxonomy_
         ix->open_chunks = 0; ix->open_peak_bytes = 0;
         {   /* short of memory with a workspace reservation in the way: hand the reservation back and try once more */
             hipError_t e = hipMalloc((void **)&ix->d_values, (T + 1) * 8);
-            if (e == hipErrorOutOfMemory && held_bytes(c) > 0) { (void)hipGetLastError(); open_make_room(c); e = hipMalloc((void **)&ix->d_values, (T + 1) * 8); }
+            if (e == hipErrorOutOfMemory && held_bytes(c, BUF_FIXED) > 0) { (void)hipGetLastError(); open_make_room(c); e = hipMalloc((void **)&ix->d_values, (T + 1) * 8); }
             HIPCHK(e);
             if (!pack) {
                 e = hipMalloc((void **)&ix->d_info, std::max<uint64_t>(T, 1) * 4);
-                if (e == hipErrorOutOfMemory && held_bytes(c) > 0) { (void)hipGetLastError(); open_make_room(c); e = hipMalloc((void **)&ix->d_info, std::max<uint64_t>(T, 1) * 4); }
+                if (e == hipErrorOutOfMemory && held_bytes(c, BUF_FIXED) > 0) { (void)hipGetLastError(); open_make_room(c); e = hipMalloc((void **)&ix->d_info, std::max<uint64_t>(T, 1) * 4); }
                 HIPCHK(e);
             }
         }
@@ -2028,13 +2046,13 @@ static mtb_status upload_reads(mtb_ctx *c, const mtb_params *p, const char *base
     if (n_reads == 0) return MTB_OK;
     if (!bases || !offs) return fail(MTB_ERR_ARG, "bases/offs NULL");
     uint64_t nb = offs[n_reads];
-    STCHK(ensure(c, "bases", nb + 8, d_b)); STCHK(ensure(c, "offs", n_reads + 1, d_o));
+    STCHK(ensure(c, "bases", nb + 8, d_b, BUF_IO)); STCHK(ensure(c, "offs", n_reads + 1, d_o, BUF_IO));
     STCHK(h2d(c, *d_b, bases, nb)); STCHK(h2d(c, *d_o, offs, (n_reads + 1) * 8));
     *n_bases = nb;
     if (p->seq_mode == 2) {
         if (!bases2 || !offs2) return fail(MTB_ERR_ARG, "seq_mode 2 needs bases2/offs2");
         uint64_t nb2 = offs2[n_reads];
-        STCHK(ensure(c, "bases2", nb2 + 8, d_b2)); STCHK(ensure(c, "offs2", n_reads + 1, d_o2));
+        STCHK(ensure(c, "bases2", nb2 + 8, d_b2, BUF_IO)); STCHK(ensure(c, "offs2", n_reads + 1, d_o2, BUF_IO));
         STCHK(h2d(c, *d_b2, bases2, nb2)); STCHK(h2d(c, *d_o2, offs2, (n_reads + 1) * 8));
         *n_bases += nb2;
     }
@@ -2051,13 +2069,14 @@ mtb_status mtb_extract(mtb_ctx *c, const mtb_params *p, const char *bases, const
     STCHK(upload_reads(c, p, bases, offs, bases2, offs2, n_reads, &d_b, &d_o, &d_b2, &d_o2, &nb));
     int32_t *d_ql, *d_ql2;
     STCHK(ensure(c, "qlen", n_reads, &d_ql)); STCHK(ensure(c, "qlen2", n_reads, &d_ql2));
-    mtb_kmer *d_k; uint64_t n;
-    STCHK(dev_extract(c, p, d_b, d_o, d_b2, d_o2, n_reads, &d_k, &n, d_ql, d_ql2, nullptr));
-    *count = n;
+    ExtractOpts two_pass; two_pass.want_max_len = false;       /* the reference's emission order; nobody asks for the longest read */
+    Extracted ex;
+    STCHK(dev_extract(c, p, Reads{d_b, d_o, d_b2, d_o2, n_reads}, d_ql, d_ql2, two_pass, &ex));
+    const uint64_t n = *count = ex.nk;
     if (qlen) STCHK(d2h(c, qlen, d_ql, n_reads * 4));
     if (qlen2) STCHK(d2h(c, qlen2, d_ql2, n_reads * 4));
     if (n > cap) return fail(MTB_ERR_CAPACITY, "k-mer buffer too small");
-    if (n) STCHK(d2h(c, out, d_k, n * sizeof(mtb_kmer)));
+    if (n) STCHK(d2h(c, out, ex.d_k, n * sizeof(mtb_kmer)));
     return MTB_OK;
 }
 
@@ -2069,7 +2088,7 @@ mtb_status mtb_sort_kmers(mtb_ctx *c, mtb_kmer *kmers, uint64_t n) {
     mtb_kmer *d_a, *d_s;
     STCHK(ensure(c, "kmersA", n, &d_a));
     STCHK(h2d(c, d_a, kmers, n * sizeof(mtb_kmer)));
-    STCHK(dev_sort(c, d_a, n, 0, &d_s));
+    STCHK(dev_sort(c, d_a, n, /* every bit */ 0, &d_s, /* binary passes: no digit array, no letter pairs */ nullptr, 0));
     STCHK(d2h(c, kmers, d_s, n * sizeof(mtb_kmer)));
     return MTB_OK;
 }
@@ -2083,7 +2102,7 @@ mtb_status mtb_match_kmers(mtb_ctx *c, mtb_index *ix, const mtb_kmer *sorted, ui
     STCHK(ensure(c, "kmersA", n, &d_q));
     STCHK(h2d(c, d_q, sorted, n * sizeof(mtb_kmer)));
     STCHK(ensure(c, "jtemp", cap, &d_m));
-    mtb_status st = dev_join(c, ix, d_q, n, d_m, cap, nullptr, count);
+    mtb_status st = dev_join(c, ix, d_q, n, MatchList{d_m, cap}, count, /* no slot segments */ nullptr, /* sorted on every bit above */ 32);
     if (st != MTB_OK) return st;
     if (*count) STCHK(d2h(c, out, d_m, *count * sizeof(mtb_match)));
     return MTB_OK;
@@ -2125,11 +2144,13 @@ mtb_status mtb_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const mtb_m
     uint32_t max_seg = 0, max_len = 0;
     for (uint64_t i = 0; i < n_reads; i++) { max_seg = std::max(max_seg, rc[i]); max_len = std::max<uint32_t>(max_len, (uint32_t)(qlen[i] + (qlen2 ? qlen2[i] : 0))); }
     mtb_result *d_res; int32_t *d_tt; uint32_t *d_tc;
-    STCHK(ensure(c, "results", n_reads, &d_res)); STCHK(ensure(c, "tctax", taxcnt_cap, &d_tt)); STCHK(ensure(c, "tccnt", taxcnt_cap, &d_tc));
+    STCHK(ensure(c, res_name(RES_ROWS, 0), n_reads, &d_res, BUF_IO)); STCHK(ensure(c, "tctax", taxcnt_cap, &d_tt, BUF_IO)); STCHK(ensure(c, "tccnt", taxcnt_cap, &d_tc, BUF_IO));
     ScoreSrc src; src.m = d_m; src.seg = d_seg; src.sort = false; src.max_seg = max_seg;
+    const ReadLens lens{d_ql, d_ql2, max_len};
+    const ResultSink out{d_res, d_tt, d_tc, taxcnt_cap, /* tc_base */ 0};
     mtb_status st = (p->seq_mode == 3 && !c->opt.no_long_scorer)
-        ? dev_score_long(c, ix, p, n_reads, d_ql, d_ql2, max_len, d_res, d_tt, d_tc, taxcnt_cap, n_taxcnt, 0, d_m, d_seg, max_seg)
-        : dev_score(c, ix, p, n_reads, d_ql, d_ql2, max_len, d_res, d_tt, d_tc, taxcnt_cap, n_taxcnt, 0, src, nullptr);
+        ? dev_score_long(c, ix, p, n_reads, lens, out, n_taxcnt, LongSegs{d_m, d_seg, max_seg})
+        : dev_score(c, ix, p, n_reads, lens, out, n_taxcnt, src, /* nothing deferred */ nullptr);
     if (st != MTB_OK) return st;
     STCHK(d2h(c, results, d_res, n_reads * sizeof(mtb_result)));
     if (*n_taxcnt) { STCHK(d2h(c, taxcnt_tax, d_tt, *n_taxcnt * 4)); STCHK(d2h(c, taxcnt_cnt, d_tc, *n_taxcnt * 4)); }
@@ -2145,10 +2166,8 @@ mtb_status mtb_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const mtb_m
  * per-read counts -> scan, regroup, big segments sorted (chunk sort in LDS + rank merges), scoring.
  * Records ev[4] (regrouped) and ev[5] (sorted). */
 static mtb_status score_join_order(mtb_ctx *c, mtb_index *ix, const mtb_params *p, mtb_match *d_tmp, uint64_t nm, uint64_t n_reads, uint32_t *d_rc,
-                                   const int32_t *d_ql, const int32_t *d_ql2, uint32_t max_len, mtb_result *d_results, int32_t *d_taxcnt_tax,
-                                   uint32_t *d_taxcnt_cnt, uint64_t taxcnt_cap, uint64_t *n_taxcnt, uint64_t tc_base) {
-    hipStream_t st = c->stream;
-    mtb_match *d_m; uint64_t *d_seg;
+                                   const ReadLens &lens, const ResultSink &out, uint64_t *n_taxcnt) {
+    hipStream_t st = c->stream; mtb_match *d_m; uint64_t *d_seg;
     STCHK(ensure(c, "matches", nm, &d_m));
     STCHK(dev_regroup(c, d_tmp, nm, n_reads, d_rc, &d_seg, d_m));
     HIPCHK(hipEventRecord(c->ev[4], st));
@@ -2159,12 +2178,12 @@ static mtb_status score_join_order(mtb_ctx *c, mtb_index *ix, const mtb_params *
     {
         uint32_t *d_large;
         STCHK(ensure(c, "large", n_reads, &d_large));
-        HIPCHK(hipMemsetAsync(c->d_scal + 2, 0, 16, st));
+        HIPCHK(scal_clear(c, SC_N_LARGE, 2));
         { KTimer kt(c, MTB_K_SEGSORT);
         hipLaunchKernelGGL(k_list_large, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, st, (const uint64_t *)d_seg, n_reads,
-                           long_scorer ? 1u : (uint32_t)MTB_SCORE_LDS, d_large, (uint32_t *)(c->d_scal + 2), (uint32_t *)(c->d_scal + 3)); }
+                           long_scorer ? 1u : (uint32_t)MTB_SCORE_LDS, d_large, scal<uint32_t>(c, SC_N_LARGE), scal<uint32_t>(c, SC_MAX_SEG)); }
         uint64_t sc[2];
-        STCHK(d2h(c, sc, c->d_scal + 2, 16));
+        STCHK(d2h(c, sc, scal<uint64_t>(c, SC_N_LARGE), 16));
         max_seg = (uint32_t)sc[1];
         if (sc[0]) {
             /* big segments: chunk sort in LDS + rank merges; the join-order buffer is the scratch */
@@ -2172,22 +2191,32 @@ static mtb_status score_join_order(mtb_ctx *c, mtb_index *ix, const mtb_params *
             HIPCHK(hipFuncSetAttribute((const void *)k_segsort_lds<mtb_match>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             KTimer kt(c, MTB_K_SEGSORT);
             hipLaunchKernelGGL((k_segsort_lds<mtb_match>), dim3(std::min<uint32_t>((uint32_t)sc[0], 2048)), dim3(MTB_SEGLDS_THREADS), lds, st, d_m,
-                               (const uint64_t *)d_seg, (const uint32_t *)d_large, (const uint32_t *)(c->d_scal + 2), d_tmp);
+                               (const uint64_t *)d_seg, (const uint32_t *)d_large, scal<const uint32_t>(c, SC_N_LARGE), d_tmp);
         }
     }
     HIPCHK(hipEventRecord(c->ev[5], st));
-    if (long_scorer) return dev_score_long(c, ix, p, n_reads, d_ql, d_ql2, max_len, d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, n_taxcnt, tc_base, d_m, d_seg, max_seg);
+    if (long_scorer) return dev_score_long(c, ix, p, n_reads, lens, out, n_taxcnt, LongSegs{d_m, d_seg, max_seg});
     ScoreSrc a; a.m = d_m; a.seg = d_seg; a.sort = true; a.max_seg = max_seg;
-    return dev_score(c, ix, p, n_reads, d_ql, d_ql2, max_len, d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, n_taxcnt, tc_base, a, nullptr);
+    return dev_score(c, ix, p, n_reads, lens, out, n_taxcnt, a, /* nothing deferred */ nullptr);
 }
 
-/* The slot segments of a short-read batch: n_reads x stride 16-byte slots in buffer "segm".  Live slots carry the batch's epoch tag;
- * the buffer is cleared only when it is new or the tag wraps. */
-static mtb_status prepare_slots(mtb_ctx *c, uint64_t n_reads, uint32_t stride, mtb_slot16 **out, uint32_t *epoch_out) {
-    hipStream_t st = c->stream;
-    mtb_slot16 *d_segm;
-    DevBuf &sb = c->bufs["segm"];
-    STCHK(ensure_placed(c, "segm", n_reads * (uint64_t)stride, &d_segm));
+static void slot_geometry(const mtb_ctx *c, uint32_t max_q, uint32_t *direct, uint32_t *stride) {
+    const uint32_t tail_min = c->opt.tail_min > 0 ? (uint32_t)std::max(8, c->opt.tail_min) & ~7u : 16u;      /* experiment switch: longer tails */
+    *direct = std::max<uint32_t>(8, (max_q + 7) & ~7u);
+    *stride = *direct + std::max<uint32_t>(tail_min, (*direct / 8 + 7) & ~7u);
+}
+/* The slot segments of a short-read batch: made once (make_slots), filled by the fused join or by k_slot_place, read by score_fixed_slots.
+ * Live slots carry the batch's epoch tag; the buffer is cleared only when it is new or the tag wraps. */
+struct SlotSegs {
+    mtb_slot16 *d_segm = nullptr; uint32_t *d_rc = nullptr, stride = 0, direct = 0, epoch = 0;       /* n_reads x stride slots in buffer "segm"; per-read tail cursors */
+    mtb_match *d_ovf = nullptr; uint64_t n_ovf = 0, ovf_region = 0;      /* the overflow list; ovf_region != 0: it is striped (dev_join) */
+    const uint8_t *d_off_reads = nullptr; uint32_t max_len_off = 0;      /* reads routed around their slots (marked by the extractor); the longest of ALL reads then */
+};
+static mtb_status make_slots(mtb_ctx *c, uint64_t n_reads, uint32_t max_q, uint32_t *d_rc, SlotSegs *sl) {
+    hipStream_t st = c->stream; *sl = SlotSegs(); sl->d_rc = d_rc;
+    slot_geometry(c, max_q, &sl->direct, &sl->stride);
+    STCHK(ensure_placed(c, "segm", n_reads * (uint64_t)sl->stride, &sl->d_segm));
+    const DevBuf sb = buf_get(c, "segm");
     const char *clear_mode = c->opt.segm_clear[0] ? c->opt.segm_clear : nullptr;      /* experiment switch: kernel | sync | always (default: hipMemsetAsync when new / on epoch wrap) */
     const bool always = clear_mode && !strcmp(clear_mode, "always");
     /* cleared when the allocation is not the one this function cleared last (new, grown, or created by mtb_ctx_reserve: never
@@ -2198,23 +2227,18 @@ static mtb_status prepare_slots(mtb_ctx *c, uint64_t n_reads, uint32_t stride, m
         if (clear_mode && !strcmp(clear_mode, "sync")) HIPCHK(hipDeviceSynchronize());
         c->seg_epoch = 0; c->seg_clean_p = sb.p; c->seg_clean_cap = sb.cap;
     }
-    c->seg_epoch++;
-    *out = d_segm; *epoch_out = c->seg_epoch;
+    sl->epoch = ++c->seg_epoch;
     return MTB_OK;
 }
-static void slot_geometry(const mtb_ctx *c, uint32_t max_q, uint32_t *direct, uint32_t *stride) {
-    const uint32_t tail_min = c->opt.tail_min > 0 ? (uint32_t)std::max(8, c->opt.tail_min) & ~7u : 16u;      /* experiment switch: longer tails */
-    *direct = std::max<uint32_t>(8, (max_q + 7) & ~7u);
-    *stride = *direct + std::max<uint32_t>(tail_min, (*direct / 8 + 7) & ~7u);
-}
+/* capacity of the overflow list "ovf": what the buffer already holds or a 64th of the items that may overflow; after an attempt that reported n entries */
+static uint64_t ovf_cap_first(mtb_ctx *c, uint64_t n_items) { return std::max<uint64_t>(buf_cap(c, "ovf") / sizeof(mtb_match), n_items / 64 + 4096); }
+static uint64_t ovf_cap_regrown(uint64_t n) { return n + n / 16 + 1024; }
 
 /* Scoring out of filled slot segments (fused path after the join; partitioned path after the matches came home): the
  * register-resident scorer, the generic one for the reads it flags, exact segments for the reads neither can take from their slots.
- * d_rc = per-read tail cursors, d_ovf / n_ovf = the overflow list.  *nm = matches seen (statistics). */
-static mtb_status score_fixed_slots(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const int32_t *d_ql, const int32_t *d_ql2, uint32_t max_len,
-                                    uint64_t nk_real, mtb_slot16 *d_segm, uint32_t *d_rc, uint32_t stride, uint32_t direct, uint32_t epoch, mtb_match *d_ovf, uint64_t n_ovf,
-                                    mtb_result *d_results, int32_t *d_taxcnt_tax, uint32_t *d_taxcnt_cnt, uint64_t taxcnt_cap, uint64_t *n_taxcnt, uint64_t tc_base, uint64_t *nm_out,
-                                    uint32_t max_len_deferred = 0, const uint8_t *d_off_reads = nullptr, uint64_t ovf_region = 0 /* != 0: the overflow list is striped (dev_join) */) {
+ * *nm_out = matches seen (statistics). */
+static mtb_status score_fixed_slots(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const ReadLens &lens, uint64_t nk_real, const SlotSegs &sl,
+                                    const ResultSink &out, uint64_t *n_taxcnt, uint64_t *nm_out) {
     hipStream_t st = c->stream;
     uint64_t nm = 0;
     memset(c->many_stats, 0, sizeof(c->many_stats));
@@ -2222,54 +2246,54 @@ static mtb_status score_fixed_slots(mtb_ctx *c, mtb_index *ix, const mtb_params 
     STCHK(ensure(c, "biglist", n_reads, &d_biglist)); STCHK(ensure(c, "bigidx", n_reads, &d_bigidx)); STCHK(ensure(c, "livecnt", n_reads, &d_cnt));
     STCHK(ensure(c, "segstart", n_reads + 1, &d_tot)); STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws2));
     HIPCHK(hipMemsetAsync(d_cnt, 0, n_reads * 4, st));
-    HIPCHK(hipMemsetAsync(c->d_scal + 2, 0, 32, st));            /* [2] unused, [3] max big segment, [5] reads deferred by the first launch */
+    HIPCHK(scal_clear(c, SC_N_UNGROUPED, 3));            /* ..., SC_MAX_BIG_SEG, SC_N_DEFERRED */
     uint64_t big_total = 0;
-    ScoreSrc a; a.m = (const mtb_match *)d_segm; a.cursor = d_rc;       /* slot mode: 16-byte slot records behind the pointer */ a.stride = stride; a.direct = direct; a.epoch = epoch; a.sort = true;
+    ScoreSrc a; a.m = (const mtb_match *)sl.d_segm; a.cursor = sl.d_rc;       /* slot mode: 16-byte slot records behind the pointer */ a.stride = sl.stride; a.direct = sl.direct; a.epoch = sl.epoch; a.sort = true; a.max_len_deferred = sl.max_len_off;
     /* LDS staging of the scorer = smallest instantiation that holds one match for every metamer of the longest read
      * (144 records: 16 waves per CU, 160: 14, 224: 10, 288: 8, 320: 7); reads with more live records are deferred */
     {   /* sized for the typical read (mean metamer count + 12 %), not the longest: the few reads beyond it take the deferred
            path, and 144 instead of 160 records is worth 10 % of the kernel on 150 bp reads (47.1 vs 52.3 ms) */
-        const uint32_t want = std::min<uint32_t>(direct, (uint32_t)((double)nk_real / (double)n_reads * 1.12) + 1);
+        const uint32_t want = std::min<uint32_t>(sl.direct, (uint32_t)((double)nk_real / (double)n_reads * 1.12) + 1);
         a.cap = want <= 144 ? 144 : want <= 160 ? 160 : want <= 224 ? 224 : want <= 288 ? 288 : 320;
     }
     a.max_seg = a.cap;
-    a.big_list = d_biglist; a.n_big = (uint32_t *)(c->d_scal + 5); a.cnt_out = d_cnt;
+    a.big_list = d_biglist; a.n_big = scal<uint32_t>(c, SC_N_DEFERRED); a.cnt_out = d_cnt;
     /* reads the first launch could not take from their slots: exact segments (live slots + overflow list), sorted in HBM */
     ScoreSecond second = [&](ScoreSrc *b, bool *go, const ScoreLaunch &SL) -> mtb_status {
         uint64_t sc = 0;
-        STCHK(d2h(c, &sc, c->d_scal + 5, 8));
+        STCHK(d2h(c, &sc, scal<uint64_t>(c, SC_N_DEFERRED), 8));
         uint32_t n_big = (uint32_t)sc;
         *go = n_big != 0;
         if (!n_big) return MTB_OK;
         c->many_stats[0] = n_big; c->many_stats[1] = 0;
         const bool no_many = c->opt.no_score_many != 0;        /* A/B switch: every deferred read through exact segments (round 4's path) */
         uint32_t *d_novf = nullptr; uint64_t *d_ostart = nullptr; mtb_match *d_ovfg = nullptr;      /* the overflow list grouped by read, once the many-species path has built it */
-        if (!no_many && stride <= 384u) {
+        if (!no_many && sl.stride <= 384u) {
             /* ---- the reads of conserved genes (kernels_score_many.h): scored straight from their slots + their overflow entries, dead
              * species dropped before anything is ordered.  The overflow list is grouped by read first (counts from the tail cursors). ---- */
             KTimer ktm(c, MTB_K_SCORE_MANY);
             uint32_t *d_ocur = nullptr, *d_rest;
             STCHK(ensure(c, "restlist", n_reads, &d_rest));
-            const bool have_ovf = ovf_region ? c->ovf_max_region != 0 : n_ovf != 0;
+            const bool have_ovf = sl.ovf_region ? c->ovf_max_region != 0 : sl.n_ovf != 0;
             if (have_ovf) {
                 STCHK(ensure(c, "novf", n_reads, &d_novf)); STCHK(ensure(c, "ocur", n_reads, &d_ocur)); STCHK(ensure(c, "ovfstart", n_reads + 1, &d_ostart));
-                STCHK(scratch(c, "ovfg", n_ovf + 1, &d_ovfg));
+                STCHK(scratch(c, "ovfg", sl.n_ovf + 1, &d_ovfg));
                 HIPCHK(hipMemsetAsync(d_ocur, 0, n_reads * 4, st));
-                hipLaunchKernelGGL(k_ovf_count, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_rc, d_off_reads, n_reads, stride - direct, d_novf);
+                hipLaunchKernelGGL(k_ovf_count, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, st, (const uint32_t *)sl.d_rc, sl.d_off_reads, n_reads, sl.stride - sl.direct, d_novf);
                 scan_launch<uint32_t, uint64_t, false>(st, d_novf, n_reads, true, d_ostart, d_ws2);
-                if (ovf_region) hipLaunchKernelGGL(k_ovf_group, dim3((uint32_t)((c->ovf_max_region + 255) / 256), MTB_OVF_STRIPES), dim3(256), 0, st, (const mtb_match *)d_ovf, n_ovf,
-                                                   (const uint64_t *)d_ostart, (const uint32_t *)d_novf, d_ocur, d_ovfg, ovf_region, (const unsigned long long *)c->d_ovfctr);
-                else hipLaunchKernelGGL(k_ovf_group, dim3((uint32_t)((n_ovf + 255) / 256)), dim3(256), 0, st, (const mtb_match *)d_ovf, n_ovf,
+                if (sl.ovf_region) hipLaunchKernelGGL(k_ovf_group, dim3((uint32_t)((c->ovf_max_region + 255) / 256), MTB_OVF_STRIPES), dim3(256), 0, st, (const mtb_match *)sl.d_ovf, sl.n_ovf,
+                                                   (const uint64_t *)d_ostart, (const uint32_t *)d_novf, d_ocur, d_ovfg, sl.ovf_region, (const unsigned long long *)c->d_ovfctr);
+                else hipLaunchKernelGGL(k_ovf_group, dim3((uint32_t)((sl.n_ovf + 255) / 256)), dim3(256), 0, st, (const mtb_match *)sl.d_ovf, sl.n_ovf,
                                         (const uint64_t *)d_ostart, (const uint32_t *)d_novf, d_ocur, d_ovfg, (uint64_t)0, (const unsigned long long *)nullptr);
             }
             unsigned long long *d_ms;                                  /* [0] reads handed on, [1] work counter, [2] matches seen, [3] survivors, [4..6] hand-over reasons */
             STCHK(ensure(c, "manystat", 16, &d_ms));
             HIPCHK(hipMemsetAsync(d_ms, 0, 16 * 8, st));
-            const bool cap192 = c->opt.many_cap ? c->opt.many_cap <= 192 : stride <= 192u;
+            const bool cap192 = c->opt.many_cap ? c->opt.many_cap <= 192 : sl.stride <= 192u;
             const uint32_t gridm = std::min<uint32_t>(n_big, 256u * (cap192 ? 12u : 7u));
-#define MTB_LAUNCH_MANY(K64, CAPV) hipLaunchKernelGGL((k_score_many<K64, CAPV>), dim3(gridm), dim3(64), 0, st, (const mtb_slot16 *)d_segm, stride, direct, epoch, (const uint32_t *)d_rc, d_off_reads, \
-            (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_biglist, (const uint32_t *)(c->d_scal + 5), SL.d_qlen, SL.d_qlen2, tax_view(ix), SL.sp, SL.d_tcoff, SL.d_res, \
-            SL.d_tc_tax, SL.d_tc_cnt, SL.tc_cap, SL.tc_base, d_rest, (uint32_t *)d_ms, d_cnt, d_ms + 1, d_ms + 2)
+#define MTB_LAUNCH_MANY(K64, CAPV) hipLaunchKernelGGL((k_score_many<K64, CAPV>), dim3(gridm), dim3(64), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads, \
+            (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_biglist, scal<const uint32_t>(c, SC_N_DEFERRED), SL.lens.d_ql, SL.lens.d_ql2, tax_view(ix), SL.sp, SL.d_tcoff, SL.out.d_res, \
+            SL.out.d_tc_tax, SL.out.d_tc_cnt, SL.out.tc_cap, SL.out.tc_base, d_rest, (uint32_t *)d_ms, d_cnt, d_ms + 1, d_ms + 2)
             if (cap192) { if (SL.key64) MTB_LAUNCH_MANY(true, 192); else MTB_LAUNCH_MANY(false, 192); }
             else { if (SL.key64) MTB_LAUNCH_MANY(true, 320); else MTB_LAUNCH_MANY(false, 320); }
 #undef MTB_LAUNCH_MANY
@@ -2288,20 +2312,20 @@ static mtb_status score_fixed_slots(mtb_ctx *c, mtb_index *ix, const mtb_params 
                 uint32_t *d_bc3, *d_segcnt, *d_rest2; uint64_t *d_bs3; uint8_t *d_todo; mtb_match *d_big3;
                 STCHK(ensure(c, "bigcnt", n_big, &d_bc3)); STCHK(ensure(c, "bigstart", (uint64_t)n_big + 1, &d_bs3)); STCHK(ensure(c, "bigseg", n_big, &d_segcnt));
                 STCHK(ensure(c, "restlist2", n_reads, &d_rest2)); STCHK(ensure(c, "todoflag", n_reads, &d_todo));
-                hipLaunchKernelGGL(k_big_count, dim3(std::min<uint32_t>(n_big, 4096)), dim3(64), 0, st, (const mtb_slot16 *)d_segm, stride, direct, epoch,
-                                   (const uint32_t *)d_rc, (const uint32_t *)d_rest, n_big, d_bc3, d_bigidx, (uint32_t *)(c->d_scal + 3), d_off_reads);
+                hipLaunchKernelGGL(k_big_count, dim3(std::min<uint32_t>(n_big, 4096)), dim3(64), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch,
+                                   (const uint32_t *)sl.d_rc, (const uint32_t *)d_rest, n_big, d_bc3, d_bigidx, scal<uint32_t>(c, SC_MAX_BIG_SEG), sl.d_off_reads);
                 scan_launch<uint32_t, uint64_t, false>(st, d_bc3, n_big, true, d_bs3, d_ws2);
                 uint64_t total3 = 0;
                 STCHK(d2h(c, &total3, d_bs3 + n_big, 8));
-                STCHK(scratch(c, "bigm", total3 + 1, &d_big3));
+                STCHK(scratch(c, "manym", total3 + 1, &d_big3));
                 HIPCHK(hipMemsetAsync(d_todo, 0, n_reads, st));
                 /* the small instantiation first (20 KB of LDS: eight workgroups per CU), the big one for the reads it flags 2 */
-                hipLaunchKernelGGL((k_many_sort<11, 2048u>), dim3(std::min<uint32_t>(n_big, 256u * 8u)), dim3(MTB_MSORT_NT), 0, st, (const mtb_slot16 *)d_segm, stride, direct, epoch, (const uint32_t *)d_rc, d_off_reads,
-                                   (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_rest, n_big, SL.d_qlen, SL.d_qlen2, SL.sp.dna_shift, (const uint64_t *)d_bs3, d_big3, d_segcnt, d_todo, 0u, 2u);
-                hipLaunchKernelGGL((k_many_sort<12, 4096u>), dim3(std::min<uint32_t>(n_big, 256u * 3u)), dim3(MTB_MSORT_NT), 0, st, (const mtb_slot16 *)d_segm, stride, direct, epoch, (const uint32_t *)d_rc, d_off_reads,
-                                   (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_rest, n_big, SL.d_qlen, SL.d_qlen2, SL.sp.dna_shift, (const uint64_t *)d_bs3, d_big3, d_segcnt, d_todo, 2u, 1u);
-                hipLaunchKernelGGL((k_score_long<2048, 256, 256, 256>), dim3(std::min<uint32_t>(n_big, 256u * 5u)), dim3(MTB_LONG_NT), 0, st, (const mtb_match *)d_big3, (const uint64_t *)d_bs3, n_reads, SL.d_qlen, SL.d_qlen2,
-                                   tax_view(ix), SL.sp, SL.d_tcoff, SL.d_res, SL.d_tc_tax, SL.d_tc_cnt, SL.tc_cap, SL.tc_base, d_todo, d_ms + 8, (const uint32_t *)d_segcnt, (const uint32_t *)d_rest, n_big);
+                hipLaunchKernelGGL((k_many_sort<11, 2048u>), dim3(std::min<uint32_t>(n_big, 256u * 8u)), dim3(MTB_MSORT_NT), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads,
+                                   (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_rest, n_big, SL.lens.d_ql, SL.lens.d_ql2, SL.sp.dna_shift, (const uint64_t *)d_bs3, d_big3, d_segcnt, d_todo, 0u, 2u);
+                hipLaunchKernelGGL((k_many_sort<12, 4096u>), dim3(std::min<uint32_t>(n_big, 256u * 3u)), dim3(MTB_MSORT_NT), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads,
+                                   (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_rest, n_big, SL.lens.d_ql, SL.lens.d_ql2, SL.sp.dna_shift, (const uint64_t *)d_bs3, d_big3, d_segcnt, d_todo, 2u, 1u);
+                hipLaunchKernelGGL((k_score_long<2048, 256, 256, 256>), dim3(std::min<uint32_t>(n_big, 256u * 5u)), dim3(MTB_LONG_NT), 0, st, (const mtb_match *)d_big3, (const uint64_t *)d_bs3, n_reads, SL.lens.d_ql, SL.lens.d_ql2,
+                                   tax_view(ix), SL.sp, SL.d_tcoff, SL.out.d_res, SL.out.d_tc_tax, SL.out.d_tc_cnt, SL.out.tc_cap, SL.out.tc_base, d_todo, d_ms + 8, (const uint32_t *)d_segcnt, (const uint32_t *)d_rest, n_big);
                 hipLaunchKernelGGL(k_list_flagged, dim3((n_big + 255) / 256), dim3(256), 0, st, (const uint32_t *)d_rest, n_big, (const uint8_t *)d_todo, (const uint32_t *)d_bc3, d_rest2, (uint32_t *)(d_ms + 9), d_cnt);
                 HIPCHK(hipGetLastError());
                 uint64_t left = 0;
@@ -2315,50 +2339,50 @@ static mtb_status score_fixed_slots(mtb_ctx *c, mtb_index *ix, const mtb_params 
             if (!n_big) return MTB_OK;
             /* what is left goes the old way: the list of those reads, its length where the launches below read it */
             d_biglist = d_rest;
-            HIPCHK(hipMemcpyAsync(c->d_scal + 5, d_nleft, 8, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(scal<uint64_t>(c, SC_N_DEFERRED), d_nleft, 8, hipMemcpyDeviceToDevice, st));
         }
         KTimer kt(c, MTB_K_SEGSORT);
         HIPCHK(hipMemsetAsync(d_bigidx, 0xFF, n_reads * 4, st));        /* reads that are not listed (k_score_many took them) own entries of the overflow list too: k_big_ovf skips them */
         STCHK(ensure(c, "bigcnt", n_big, &d_bigcnt)); STCHK(ensure(c, "bigstart", (uint64_t)n_big + 1, &d_bigstart)); STCHK(ensure(c, "bigcur", n_big, &d_bigcur));
-        hipLaunchKernelGGL(k_big_count, dim3(std::min<uint32_t>(n_big, 4096)), dim3(64), 0, st, (const mtb_slot16 *)d_segm, stride, direct, epoch,
-                           (const uint32_t *)d_rc, (const uint32_t *)d_biglist, n_big, d_bigcnt, d_bigidx, (uint32_t *)(c->d_scal + 3), d_off_reads,
-                           (const uint32_t *)(d_ovfg ? d_novf : nullptr), (unsigned long long *)(c->d_scal + 2));
+        hipLaunchKernelGGL(k_big_count, dim3(std::min<uint32_t>(n_big, 4096)), dim3(64), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch,
+                           (const uint32_t *)sl.d_rc, (const uint32_t *)d_biglist, n_big, d_bigcnt, d_bigidx, scal<uint32_t>(c, SC_MAX_BIG_SEG), sl.d_off_reads,
+                           (const uint32_t *)(d_ovfg ? d_novf : nullptr), scal<unsigned long long>(c, SC_N_UNGROUPED));
         scan_launch<uint32_t, uint64_t, false>(st, d_bigcnt, n_big, true, d_bigstart, d_ws2);
         uint64_t mx = 0, n_ungrouped = 0;
         STCHK(d2h(c, &big_total, d_bigstart + n_big, 8));
-        STCHK(d2h(c, &mx, c->d_scal + 3, 8));
-        STCHK(d2h(c, &n_ungrouped, c->d_scal + 2, 8));
+        STCHK(d2h(c, &mx, scal<uint64_t>(c, SC_MAX_BIG_SEG), 8));
+        STCHK(d2h(c, &n_ungrouped, scal<uint64_t>(c, SC_N_UNGROUPED), 8));
         STCHK(scratch(c, "bigm", big_total, &d_big));
-        hipLaunchKernelGGL(k_big_copy, dim3(std::min<uint32_t>(n_big, 4096)), dim3(64), 0, st, (const mtb_slot16 *)d_segm, stride, direct, epoch,
-                           (const uint32_t *)d_rc, (const uint32_t *)d_biglist, (const uint64_t *)d_bigstart, n_big, d_bigcur, d_big,
+        hipLaunchKernelGGL(k_big_copy, dim3(std::min<uint32_t>(n_big, 4096)), dim3(64), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch,
+                           (const uint32_t *)sl.d_rc, (const uint32_t *)d_biglist, (const uint64_t *)d_bigstart, n_big, d_bigcur, d_big,
                            (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)(d_ovfg ? d_novf : nullptr));
         /* the pass over the whole overflow list: only for listed reads whose entries are not in the grouped list (all of them when there is none) */
         const uint32_t *skip_grouped = d_ovfg ? d_novf : nullptr;
         if (d_ovfg && n_ungrouped == 0) { /* every listed read's entries came from its group */ }
-        else if (ovf_region) {            /* striped list (the directory join's): every stripe's entries */
-            if (c->ovf_max_region) hipLaunchKernelGGL(k_big_ovf, dim3((uint32_t)((c->ovf_max_region + 255) / 256), MTB_OVF_STRIPES), dim3(256), 0, st, (const mtb_match *)d_ovf, n_ovf,
-                                                      (const uint32_t *)d_bigidx, (const uint64_t *)d_bigstart, d_bigcur, d_big, ovf_region, (const unsigned long long *)c->d_ovfctr, skip_grouped);
+        else if (sl.ovf_region) {            /* striped list (the directory join's): every stripe's entries */
+            if (c->ovf_max_region) hipLaunchKernelGGL(k_big_ovf, dim3((uint32_t)((c->ovf_max_region + 255) / 256), MTB_OVF_STRIPES), dim3(256), 0, st, (const mtb_match *)sl.d_ovf, sl.n_ovf,
+                                                      (const uint32_t *)d_bigidx, (const uint64_t *)d_bigstart, d_bigcur, d_big, sl.ovf_region, (const unsigned long long *)c->d_ovfctr, skip_grouped);
         } else
-        if (n_ovf) hipLaunchKernelGGL(k_big_ovf, dim3((uint32_t)((n_ovf + 255) / 256)), dim3(256), 0, st, (const mtb_match *)d_ovf, n_ovf,
+        if (sl.n_ovf) hipLaunchKernelGGL(k_big_ovf, dim3((uint32_t)((sl.n_ovf + 255) / 256)), dim3(256), 0, st, (const mtb_match *)sl.d_ovf, sl.n_ovf,
                                       (const uint32_t *)d_bigidx, (const uint64_t *)d_bigstart, d_bigcur, d_big, (uint64_t)0, (const unsigned long long *)nullptr, skip_grouped);
         /* segments of up to 512 matches (nearly all: a read of a conserved gene brings a few hundred) are sorted in LDS by one wave
          * each; only the ones beyond go through the HBM-resident bitonic network (36 global-memory stages for 256 records: it cost
          * ~70 us per segment, and 7 % of the reads of a realistic batch come here) */
         uint32_t *d_lg;
         STCHK(ensure(c, "large", n_big, &d_lg));
-        HIPCHK(hipMemsetAsync(c->d_xscal + 2, 0, 8, st));
+        HIPCHK(scal_clear(c, SC_DEFER_N_LARGE));
         hipLaunchKernelGGL(k_segsort_small, dim3(std::min<uint32_t>(n_big, 256u * 40u)), dim3(64), 0, st, d_big, (const uint64_t *)d_bigstart, (uint64_t)n_big, d_lg,
-                           (uint32_t *)(c->d_xscal + 2), (uint32_t *)nullptr);
+                           scal<uint32_t>(c, SC_DEFER_N_LARGE), (uint32_t *)nullptr);
         hipLaunchKernelGGL((k_segsort_large<mtb_match>), dim3(std::min<uint32_t>(n_big, 1024)), dim3(256), 0, st, d_big, (const uint64_t *)d_bigstart,
-                           (const uint32_t *)d_lg, (const uint32_t *)(c->d_xscal + 2));
+                           (const uint32_t *)d_lg, scal<const uint32_t>(c, SC_DEFER_N_LARGE));
         HIPCHK(hipGetLastError());
-        b->m = d_big; b->seg = d_bigstart; b->list = d_biglist; b->n_list = (const uint32_t *)(c->d_scal + 5); b->seg_by_list = 1;
+        b->m = d_big; b->seg = d_bigstart; b->list = d_biglist; b->n_list = scal<const uint32_t>(c, SC_N_DEFERRED); b->seg_by_list = 1;
         /* one wave per workgroup, 14 of them resident per CU: a thousand workgroups left three quarters of the chip idle when hundreds of
          * thousands of reads come here (reads of conserved genes: hundreds of matches each); the slab pool stays bounded by dev_score */
         b->sort = false; b->max_seg = (uint32_t)mx; b->grid = std::min<uint32_t>(n_big, 256u * 14u); b->cap = 320;
         return MTB_OK;
     };
-    STCHK(dev_score(c, ix, p, n_reads, d_ql, d_ql2, max_len, d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, n_taxcnt, tc_base, a, &second, max_len_deferred));
+    STCHK(dev_score(c, ix, p, n_reads, lens, out, n_taxcnt, a, &second));
     /* number of matches (statistics): live records seen by the first launch + the deferred reads' segments */
     { KTimer kt(c, MTB_K_SCAN); scan_launch<uint32_t, uint64_t, false>(st, d_cnt, n_reads, true, d_tot, d_ws2); }
     STCHK(d2h(c, &nm, d_tot + n_reads, 8));
@@ -2377,7 +2401,7 @@ static mtb_status download_packed(mtb_ctx *c, mtb_result *d_res, const int32_t *
     uint64_t total = 0;
     STCHK(d2h(c, &total, d_off + n_reads, 8));
     if (total > host_cap) { *n_taxcnt = total; return fail(MTB_ERR_CAPACITY, "taxcnt arrays too small for the batch's taxID:count lists"); }
-    STCHK(ensure(c, async_set == 1 ? "tctax2b" : "tctax2", total, &d_tt2)); STCHK(ensure(c, async_set == 1 ? "tccnt2b" : "tccnt2", total, &d_tc2));
+    STCHK(ensure(c, res_name(RES_TAX, async_set == 1), total, &d_tt2)); STCHK(ensure(c, res_name(RES_CNT, async_set == 1), total, &d_tc2));
     hipLaunchKernelGGL(k_taxcnt_pack, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, c->stream, d_res, n_reads, (const uint64_t *)d_off, d_tt, d_tc, d_tt2, d_tc2);
     HIPCHK(hipGetLastError());
     if (async_set >= 0) {
@@ -2397,240 +2421,227 @@ static mtb_status download_packed(mtb_ctx *c, mtb_result *d_res, const int32_t *
     return MTB_OK;
 }
 
-/* one read range on one stream; taxcnt slots of this range start at tc_base of the caller's arrays */
-static mtb_status classify_one(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const char *d_bases, const uint64_t *d_offs,
-                               const char *d_bases2, const uint64_t *d_offs2, uint64_t n_reads, uint64_t n_bases_total,
-                               mtb_result *d_results, int32_t *d_taxcnt_tax, uint32_t *d_taxcnt_cnt, uint64_t taxcnt_cap,
-                               uint64_t *n_taxcnt, uint64_t tc_base) {
+/* the sorted query metamers of a read range, and what the extractor said about them */
+struct SortedQueries {
+    const mtb_kmer *d_s = nullptr; uint64_t nk = 0; int low_bits = 32;       /* low_bits: the bits the list is NOT sorted on (the join's tile windows follow the sort key) */
+    uint32_t max_q = 0; const uint32_t *d_counts = nullptr;                  /* most metamers of a read (of those that use the slots); metamers per read (long-read slot path) */
+};
+/* What the slot join leaves dead until the next batch's extraction, for scratch(): the metamer buffer that does NOT hold the sorted list (that one is looked at after the batch), both digit arrays */
+static void set_dead_segments(mtb_ctx *c, const mtb_kmer *d_sorted) {
+    c->n_dead = 0;
+    const size_t least = c->opt.scratch_alias > 0 ? 1 : (64u << 20);
+    for (const char *name : {"kmersA", "kmersB", "digA", "digB"}) {
+        const DevBuf b = buf_get(c, name);
+        if (c->opt.scratch_alias < 0 || !b.p || b.p == (const void *)d_sorted || b.cap < least || c->n_dead == 3) continue;
+        c->dead[c->n_dead++] = {(char *)b.p, b.cap, 0};
+    }
+}
+/* Long reads on ordinal slots: join into per-read slot ranges, order every range by a stable species partition (k_seg_order), score.
+ * *done = false (nothing scored): some read overran even the long tails; the caller redoes the range on exact segments. */
+static mtb_status score_long_slots(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const ReadLens &lens, const SortedQueries &q,
+                                   const ResultSink &out, uint64_t *n_taxcnt, uint64_t *nm_out, bool *done) {
+    hipStream_t st = c->stream; uint32_t *d_sizes, *d_live, *d_fail, *d_rc; uint64_t *d_rb, *d_ws2;
+    STCHK(ensure(c, "lsizes", n_reads, &d_sizes)); STCHK(ensure(c, "lrb", n_reads + 1, &d_rb)); STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws2));
+    STCHK(ensure(c, "livecnt", n_reads, &d_live)); STCHK(ensure(c, "lfail", n_reads, &d_fail)); STCHK(ensure(c, "readcnt", n_reads, &d_rc));     /* the join's per-read cursors */
+    *done = false;
+    /* tail = a quarter of the read's metamers, then all of them; a context whose last batch needed the long tails starts with them
+     * (a database with long candidate runs overflows the short ones batch after batch: the join ran twice every time) */
+    for (uint32_t tf = c->lslot_tf_start; tf <= 4 && !*done; tf *= 4) {
+        hipLaunchKernelGGL(k_lslot_sizes, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, st, (const uint32_t *)q.d_counts, n_reads, tf, d_sizes);
+        { KTimer kt(c, MTB_K_SCAN); scan_launch<uint32_t, uint64_t, false>(st, d_sizes, n_reads, true, d_rb, d_ws2); }
+        uint64_t n_slots = 0;
+        STCHK(d2h(c, &n_slots, d_rb + n_reads, 8));
+        mtb_slot16 *d_segm; mtb_match *d_m; STCHK(ensure(c, "segm", n_slots, &d_segm));
+        c->seg_epoch = MTB_SLOT_EPOCHS;                           /* (a later short-read batch starts from a cleared buffer) */
+        HIPCHK(hipMemsetAsync(d_segm, 0, n_slots * sizeof(mtb_slot16), st));
+        HIPCHK(hipMemsetAsync(d_rc, 0, n_reads * 4, st));
+        JoinSegArgs sa; memset(&sa, 0, sizeof(sa)); uint64_t n_ovf = 0;
+        sa.seg = d_segm; sa.cursor = d_rc; sa.rb = d_rb; sa.dcnt = q.d_counts; sa.tf = tf; sa.ovf = nullptr; sa.ovf_cap = 0;
+        mtb_status s2 = dev_join(c, ix, q.d_s, q.nk, MatchList(), &n_ovf, &sa, q.low_bits);
+        if (s2 == MTB_ERR_CAPACITY) {                              /* some read's tail overran: larger tails */
+            c->lslot_tf_start = 4;
+            if (c->opt.lslot_verbose) fprintf(stderr, "mtb: long-read slot path: %llu matches beyond the tails at tail factor %u/4\n", (unsigned long long)n_ovf, tf);
+            continue;
+        }
+        if (s2 != MTB_OK) return s2;
+        HIPCHK(hipEventRecord(c->ev[3], st));
+        STCHK(ensure(c, "matches", n_slots, &d_m));
+        HIPCHK(scal_clear(c, SC_LS_N_FAIL, 2));         /* ... and SC_LS_N_ALL */
+        HIPCHK(scal_clear(c, SC_LS_WORK));
+        { KTimer kt(c, MTB_K_SEGSORT);
+          hipLaunchKernelGGL(k_seg_order, dim3((uint32_t)std::min<uint64_t>(n_reads, 256ull * 2)), dim3(MTB_SO_NT), 0, st, (const mtb_slot16 *)d_segm, (const uint64_t *)d_rb,
+                             (const uint32_t *)q.d_counts, (const uint32_t *)d_rc, tf, n_reads, d_m, d_live, scal<uint32_t>(c, SC_LS_N_FAIL), d_fail, scal<unsigned long long>(c, SC_LS_WORK),
+                             scal<unsigned long long>(c, SC_LS_N_ALL)); }
+        HIPCHK(hipGetLastError());
+#ifdef MTB_SO_PHASE_CYCLES
+        {   HIPCHK(hipStreamSynchronize(st));
+            unsigned long long h[8], z[8] = {0};
+            HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(mtb_so_cycles), sizeof(h)));
+            HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(mtb_so_cycles), z, sizeof(z)));
+            static const char *nm[8] = {"claim + clear", "pass 1 (bits)", "pass 2 (counts, tail keys)", "single-match species", "tail sort", "species sort + offsets", "scatter pass", "tail pass"};
+            unsigned long long tot = 0; for (int k = 0; k < 8; k++) tot += h[k];
+            fprintf(stderr, "k_seg_order phases (%llu reads):", (unsigned long long)n_reads);
+            for (int k = 0; k < 8; k++) fprintf(stderr, " %s %.1f %%;", nm[k], tot ? 100.0 * (double)h[k] / (double)tot : 0.0);
+            fprintf(stderr, "\n");
+        }
+#endif
+        uint64_t sc2[2] = {0, 0};
+        STCHK(d2h(c, sc2, scal<uint64_t>(c, SC_LS_N_FAIL), 16));
+        if (c->opt.lslot_verbose) fprintf(stderr, "mtb: long-read slot path: %llu reads, tail factor %u/4, %llu slots, %llu matches, %llu reads beyond the LDS tables (sorted the general way)\n",
+                                                 (unsigned long long)n_reads, tf, (unsigned long long)n_slots, (unsigned long long)sc2[1], (unsigned long long)(sc2[0] & 0xFFFFFFFFull));
+        const uint32_t n_failed = (uint32_t)(sc2[0] & 0xFFFFFFFFull);
+        /* reads beyond k_seg_order's LDS tables: their live slots -> exact segments, sorted the general way */
+        mtb_match *d_big = nullptr; uint64_t *d_bigstart = nullptr; uint32_t big_max = 0; uint64_t big_total = 0;
+        if (n_failed) {
+            uint32_t *d_bigcnt; mtb_match *d_scr; uint64_t mx = 0;
+            STCHK(ensure(c, "bigcnt", n_failed, &d_bigcnt)); STCHK(ensure(c, "bigstart", (uint64_t)n_failed + 1, &d_bigstart));
+            HIPCHK(scal_clear(c, SC_LS_MAX_SEG));
+            hipLaunchKernelGGL(k_lbig_count, dim3(std::min<uint32_t>(n_failed, 4096)), dim3(64), 0, st, (const mtb_slot16 *)d_segm, (const uint64_t *)d_rb, (const uint32_t *)q.d_counts,
+                               (const uint32_t *)d_rc, tf, (const uint32_t *)d_fail, n_failed, d_bigcnt, scal<uint32_t>(c, SC_LS_MAX_SEG));
+            scan_launch<uint32_t, uint64_t, false>(st, d_bigcnt, n_failed, true, d_bigstart, d_ws2);
+            STCHK(d2h(c, &big_total, d_bigstart + n_failed, 8));
+            STCHK(d2h(c, &mx, scal<uint64_t>(c, SC_LS_MAX_SEG), 8));
+            big_max = (uint32_t)mx;
+            STCHK(ensure(c, "lbigm", big_total, &d_big)); STCHK(ensure(c, "jtemp", big_total, &d_scr));
+            hipLaunchKernelGGL(k_lbig_copy, dim3(std::min<uint32_t>(n_failed, 4096)), dim3(64), 0, st, (const mtb_slot16 *)d_segm, (const uint64_t *)d_rb, (const uint32_t *)q.d_counts,
+                               (const uint32_t *)d_rc, tf, (const uint32_t *)d_fail, n_failed, (const uint64_t *)d_bigstart, d_big);
+            const size_t lds = (size_t)MTB_SEGLDS_CHUNK * 14;
+            HIPCHK(hipFuncSetAttribute((const void *)k_segsort_lds<mtb_match>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            { KTimer kt(c, MTB_K_SEGSORT);
+              hipLaunchKernelGGL((k_segsort_lds<mtb_match>), dim3(std::min<uint32_t>(n_failed, 2048)), dim3(MTB_SEGLDS_THREADS), lds, st, d_big, (const uint64_t *)d_bigstart,
+                                 (const uint32_t *)nullptr, scal<const uint32_t>(c, SC_LS_N_FAIL), d_scr); }
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(c->ev[4], st)); HIPCHK(hipEventRecord(c->ev[5], st));
+        STCHK(dev_score_long(c, ix, p, n_reads, lens, out, n_taxcnt, LongSegs{d_m, d_rb, q.max_q + mtb_lslot_tail(q.max_q, tf), d_live}));
+        uint64_t n_generic = 0;
+        if (n_failed) {
+            STCHK(d2h(c, &n_generic, scal<uint64_t>(c, SC_N_GENERIC), 8));        /* reads the first launch left to the generic kernel */
+            uint64_t n_tc2 = 0, g2 = 0;
+            STCHK(dev_score_long(c, ix, p, n_reads, lens, out, &n_tc2, LongSegs{d_big, d_bigstart, big_max, /* d_segcnt */ nullptr, d_fail, n_failed}));
+            STCHK(d2h(c, &g2, scal<uint64_t>(c, SC_N_GENERIC), 8));
+            n_generic = (n_generic & 0xFFFFFFFFull) + (g2 & 0xFFFFFFFFull);
+            STCHK(h2d(c, scal<uint64_t>(c, SC_N_GENERIC), &n_generic, 8));
+        }
+        *nm_out = sc2[1] + big_total; *done = true;
+    }
+    return MTB_OK;
+}
+/* One attempt at one read range on one stream; taxcnt slots of this range start at out.tc_base of the caller's arrays.  long_slots: long reads may take
+ * the ordinal-slot path; *redo_exact is set (nothing scored) when its slot ranges overflowed: classify_one comes again without them. */
+static mtb_status classify_attempt(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const Reads &rd, const ResultSink &out, uint64_t *n_taxcnt, bool long_slots, bool *redo_exact) {
     HIPCHK(hipSetDevice(c->device));
-    *n_taxcnt = 0;
-    memset(&c->stats, 0, sizeof(c->stats));
+    *n_taxcnt = 0; *redo_exact = false;
     collect_kernel_times(c);          /* drop events of stage-level calls */
     memset(&c->stats, 0, sizeof(c->stats));
+    const uint64_t n_reads = rd.n_reads;
     if (n_reads == 0) return MTB_OK;
-    hipStream_t st = c->stream;
-    int32_t *d_ql, *d_ql2;
+    hipStream_t st = c->stream; int32_t *d_ql, *d_ql2;
     STCHK(ensure(c, "qlen", n_reads, &d_ql)); STCHK(ensure(c, "qlen2", n_reads, &d_ql2));
     HIPCHK(hipEventRecord(c->ev[0], st));
-    mtb_kmer *d_k; uint64_t nk; uint32_t max_len = 0, max_q = 0;
-    uint64_t nk_real = 0;                 /* nk counts the blank tail records of the single-pass extraction too */
     /* short reads: per-read slot segments, the query's ordinal (tagged into qinfo by the extractor) is the slot of its
      * first match.  Needs positions < 2^12 (16-byte slot records) and a moderate number of metamers per read; otherwise
      * exact segments. */
     bool fixed = p->seq_mode != 3;
     /* long reads: ordinal slots too, with per-read slot ranges (k_join_dir<.., LONG>, kernels_seg_order.h) -- needs the directory join,
      * positions and ordinals below 2^16; otherwise (and after a failed attempt) exact segments via regroup + segment sort */
-    bool lslot = p->seq_mode == 3 && ix->d_dir && !c->no_lslot && !c->opt.no_long_slots;
-    uint32_t *d_dcnt = nullptr;
-    if (lslot) { STCHK(ensure(c, "dcnt", n_reads, &d_dcnt)); HIPCHK(hipMemsetAsync(d_dcnt, 0, n_reads * 4, st)); }
-    uint16_t *d_dig = nullptr;               /* first radix pass's digits, written by the single-pass extractor */
-    const bool aa6 = p->kmer_format == 2;           /* 5-bit amino-acid letters: three base-21 pair passes order bits [34,64) */
-    uint64_t n_bases_exact = n_bases_total;      /* the caller's figure is an estimate for a sub-batch of variable-length reads: the budget is kept on the exact one */
+    bool lslot = p->seq_mode == 3 && ix->d_dir && long_slots && !c->opt.no_long_slots;
+    const bool aa6 = p->kmer_format == 2;           /* 5-bit amino-acid letters: three base-21 pair passes order bits [34,64); the single-pass extractor writes the first pass's digits */
+    ExtractOpts xo; xo.single_pass = true; xo.tag_ordinals = fixed || lslot; xo.want_digits = aa6;
+    if (lslot) { STCHK(ensure(c, "dcnt", n_reads, &xo.d_counts)); HIPCHK(hipMemsetAsync(xo.d_counts, 0, n_reads * 4, st)); }
     /* short-read batches: reads whose positions do not fit a slot record (>= 4093 used bases) or that carry more metamers than a segment
      * has direct slots for are marked by the extractor and routed AROUND the slot segments one by one (join: overflow list; scoring:
      * exact segments) -- a handful of long reads in an Illumina batch no longer send the whole batch down the exact-segment path */
-    uint8_t *d_off = nullptr; uint64_t off_stats[3] = {0, 0, 0};
-    if (fixed && ix->d_dir) STCHK(ensure(c, "offreads", n_reads, &d_off));
-    STCHK(dev_extract(c, p, d_bases, d_offs, d_bases2, d_offs2, n_reads, &d_k, &nk, d_ql, d_ql2, &max_len, true, n_bases_total, &nk_real, fixed || lslot, &max_q, aa6 ? &d_dig : nullptr, d_dcnt, &n_bases_exact,
-                      d_off, off_stats));
-    uint32_t max_len_all = max_len;
-    bool route_off = false;
-    if (fixed && d_off && off_stats[1] > 0 && off_stats[1] * 4 <= n_reads && max_len + 3 < 65536u && max_q < 65535u && off_stats[1] < n_reads) {
+    if (fixed && ix->d_dir) STCHK(ensure(c, "offreads", n_reads, &xo.d_off_reads));
+    Extracted ex; STCHK(dev_extract(c, p, rd, d_ql, d_ql2, xo, &ex));
+    ReadLens lens{d_ql, d_ql2, ex.max_len};
+    uint32_t max_q = ex.max_q; const uint32_t max_len_all = ex.max_len; bool route_off = false;
+    if (fixed && xo.d_off_reads && ex.off_reads > 0 && ex.off_reads * 4 <= n_reads && ex.max_len + 3 < 65536u && max_q < 65535u && ex.off_reads < n_reads) {
         route_off = true;
-        max_q = (uint32_t)off_stats[0]; max_len = (uint32_t)off_stats[2];       /* the slot geometry and the first scoring launch follow the reads that use the slots */
+        max_q = (uint32_t)ex.off_max_q; lens.max_len = (uint32_t)ex.off_max_len;       /* the slot geometry and the first scoring launch follow the reads that use the slots */
     }
-    if ((fixed && !route_off && (max_len + 3 >= MTB_SLOT_MAX_POS || max_q > MTB_SLOT_MAX_Q)) || (lslot && (max_len + 3 >= 65536u || max_q >= 65535u))) {
+    if ((fixed && !route_off && (lens.max_len + 3 >= MTB_SLOT_MAX_POS || max_q > MTB_SLOT_MAX_Q)) || (lslot && (lens.max_len + 3 >= 65536u || max_q >= 65535u))) {
         fixed = false; lslot = false;      /* tags would collide with positions / segments would be huge: extract again untagged */
-        STCHK(dev_extract(c, p, d_bases, d_offs, d_bases2, d_offs2, n_reads, &d_k, &nk, d_ql, d_ql2, &max_len, true, n_bases_total, &nk_real, false, &max_q, aa6 ? &d_dig : nullptr));
+        ExtractOpts untagged; untagged.single_pass = true; untagged.want_digits = aa6;
+        STCHK(dev_extract(c, p, rd, d_ql, d_ql2, untagged, &ex));
+        lens.max_len = ex.max_len; max_q = ex.max_q;
     }
     HIPCHK(hipEventRecord(c->ev[1], st));
     /* the join needs tiles with a narrow amino-acid range, not a total order: kmer_format 2 sorts on the first six
      * amino-acid letters (three base-21 pair passes = bits [34,64)), kmer_format 1 on the top 32 bits (four binary
      * passes; three binary passes make the tiles too wide for the LDS window, measured); the tile's target window
      * comes from k_join_bounds */
-    mtb_kmer *d_s;
     int aa_first_shift = 34;
     if (aa6 && fixed && ix->d_dir && c->opt.sort_pairs > 0) aa_first_shift = 64 - 10 * std::max(1, std::min(3, c->opt.sort_pairs));
-    const int low_bits = aa6 ? aa_first_shift : 32;          /* the bits the list is NOT sorted on (the join's tile windows follow the sort key) */
-    STCHK(dev_sort(c, d_k, nk, aa6 ? MTB_SORT_AA6 : 32, &d_s, aa_first_shift == 34 ? d_dig : nullptr, aa_first_shift));
+    mtb_kmer *d_s; uint32_t *d_rc;
+    STCHK(dev_sort(c, ex.d_k, ex.nk, aa6 ? MTB_SORT_AA6 : 32, &d_s, aa_first_shift == 34 ? ex.d_dig : nullptr, aa_first_shift));
     HIPCHK(hipEventRecord(c->ev[2], st));
-    c->last_sorted = (fixed && ix->d_dir) ? d_s : nullptr; c->last_sorted_n = nk;
-    uint32_t *d_rc;
+    SortedQueries q; q.d_s = d_s; q.nk = ex.nk; q.low_bits = aa6 ? aa_first_shift : 32; q.max_q = max_q; q.d_counts = xo.d_counts;
+    c->last_sorted = (fixed && ix->d_dir) ? d_s : nullptr; c->last_sorted_n = ex.nk;
     STCHK(ensure(c, "readcnt", n_reads, &d_rc));
     HIPCHK(hipMemsetAsync(d_rc, 0, n_reads * 4, st));
     uint64_t nm = 0;
     if (fixed) {
-        /* ---- join straight into per-read slot segments (d_rc = per-read tail cursor) ---- */
-        uint32_t direct, stride;
-        slot_geometry(c, max_q, &direct, &stride);
-        mtb_slot16 *d_segm; mtb_match *d_ovf; uint64_t n_ovf = 0; uint32_t epoch = 0;
-        STCHK(prepare_slots(c, n_reads, stride, &d_segm, &epoch));
-        DevBuf &ob = c->bufs["ovf"];
-        uint64_t ovf_cap = std::max<uint64_t>(ob.cap / sizeof(mtb_match), nk / 64 + 4096);
-        for (int attempt = 0; attempt < 3; attempt++) {
-            STCHK(ensure(c, "ovf", ovf_cap, &d_ovf));
+        /* ---- join straight into per-read slot segments, score out of them ---- */
+        SlotSegs sl;
+        STCHK(make_slots(c, n_reads, max_q, d_rc, &sl));
+        if (route_off) { sl.d_off_reads = xo.d_off_reads; sl.max_len_off = max_len_all; }
+        uint64_t ovf_cap = ovf_cap_first(c, q.nk);
+        for (int attempt = 0; attempt < 3; attempt++) {       /* the overflow list regrown to what the failed attempt reported */
+            STCHK(ensure(c, "ovf", ovf_cap, &sl.d_ovf));
             JoinSegArgs sa; memset(&sa, 0, sizeof(sa));
-            sa.seg = d_segm; sa.stride = stride; sa.direct = direct; sa.cursor = d_rc; sa.ovf = d_ovf; sa.ovf_cap = ovf_cap;
-            sa.ovf_counter = nullptr; sa.epoch = epoch; sa.off = route_off ? d_off : nullptr;
+            sa.seg = sl.d_segm; sa.stride = sl.stride; sa.direct = sl.direct; sa.cursor = d_rc; sa.ovf = sl.d_ovf; sa.ovf_cap = ovf_cap;
+            sa.ovf_counter = nullptr; sa.epoch = sl.epoch; sa.off = sl.d_off_reads;
             sa.dense_ovf = attempt == 2 ? 1u : 0u;            /* last attempt: one list that holds the total, whatever the stripes' fill */
             sa.retry = attempt > 0 ? 1u : 0u;
-            mtb_status s2 = dev_join(c, ix, d_s, nk, nullptr, 0, nullptr, &n_ovf, &sa, low_bits);
+            mtb_status s2 = dev_join(c, ix, q.d_s, q.nk, MatchList(), &sl.n_ovf, &sa, q.low_bits);
             if (s2 == MTB_OK) break;
             if (s2 != MTB_ERR_CAPACITY || attempt == 2) return s2;
-            ovf_cap = n_ovf + n_ovf / 16 + 1024;
+            ovf_cap = ovf_cap_regrown(sl.n_ovf);
             HIPCHK(hipMemsetAsync(d_rc, 0, n_reads * 4, st));     /* ordinal slots are rewritten identically; tail slots and the overflow list are filled anew (their order follows the atomics) */
         }
-        HIPCHK(hipEventRecord(c->ev[3], st));
-        HIPCHK(hipEventRecord(c->ev[4], st));
-        HIPCHK(hipEventRecord(c->ev[5], st));
-        {   /* dead from here to the next extraction (the sorted list itself stays: mtb_ctx_join_footprint / mtb_ctx_query_runs look at it after the batch) */
-            std::lock_guard<std::mutex> lk(c->bufs_mu);
-            c->n_dead = 0;
-            const size_t least = c->opt.scratch_alias > 0 ? 1 : (64u << 20);
-            for (const char *nm : {"kmersA", "kmersB", "digA", "digB"}) {
-                auto it = c->bufs.find(nm);
-                if (c->opt.scratch_alias < 0 || it == c->bufs.end() || !it->second.p || it->second.p == (void *)d_s || it->second.cap < least || c->n_dead == 3) continue;
-                c->dead[c->n_dead].p = (char *)it->second.p; c->dead[c->n_dead].cap = it->second.cap; c->dead[c->n_dead].used = 0; c->n_dead++;
-            }
-        }
+        sl.ovf_region = c->ovf_region;
+        for (int k = 3; k <= 5; k++) HIPCHK(hipEventRecord(c->ev[k], st));
+        set_dead_segments(c, d_s);
         struct DeadEnd { mtb_ctx *c; ~DeadEnd() { c->n_dead = 0; } } dead_end{c};
-        STCHK(score_fixed_slots(c, ix, p, n_reads, d_ql, d_ql2, max_len, nk_real, d_segm, d_rc, stride, direct, epoch, d_ovf, n_ovf,
-                                d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, n_taxcnt, tc_base, &nm, route_off ? max_len_all : 0, route_off ? d_off : nullptr, c->ovf_region));
+        STCHK(score_fixed_slots(c, ix, p, n_reads, lens, ex.nk_real, sl, out, n_taxcnt, &nm));
     } else if (lslot) {
-        /* ---- long reads on ordinal slots: join into per-read slot ranges, order every range by a stable species partition, score ---- */
-        uint32_t *d_sizes; uint64_t *d_rb, *d_ws2; uint32_t *d_live;
-        STCHK(ensure(c, "lsizes", n_reads, &d_sizes)); STCHK(ensure(c, "lrb", n_reads + 1, &d_rb)); STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws2));
-        STCHK(ensure(c, "livecnt", n_reads, &d_live));
-        uint32_t *d_fail;
-        STCHK(ensure(c, "lfail", n_reads, &d_fail));
         bool done = false;
-        /* tail = a quarter of the read's metamers, then all of them; a context whose last batch needed the long tails starts with them
-         * (a database with long candidate runs overflows the short ones batch after batch: the join ran twice every time) */
-        for (uint32_t tf = c->lslot_tf_start; tf <= 4 && !done; tf *= 4) {
-            hipLaunchKernelGGL(k_lslot_sizes, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, st, (const uint32_t *)d_dcnt, n_reads, tf, d_sizes);
-            { KTimer kt(c, MTB_K_SCAN); scan_launch<uint32_t, uint64_t, false>(st, d_sizes, n_reads, true, d_rb, d_ws2); }
-            uint64_t n_slots = 0;
-            STCHK(d2h(c, &n_slots, d_rb + n_reads, 8));
-            mtb_slot16 *d_segm; mtb_match *d_m;
-            STCHK(ensure(c, "segm", n_slots, &d_segm));
-            c->seg_epoch = MTB_SLOT_EPOCHS;                           /* (a later short-read batch starts from a cleared buffer) */
-            HIPCHK(hipMemsetAsync(d_segm, 0, n_slots * sizeof(mtb_slot16), st));
-            HIPCHK(hipMemsetAsync(d_rc, 0, n_reads * 4, st));
-            JoinSegArgs sa; memset(&sa, 0, sizeof(sa));
-            sa.seg = d_segm; sa.cursor = d_rc; sa.rb = d_rb; sa.dcnt = d_dcnt; sa.tf = tf; sa.ovf = nullptr; sa.ovf_cap = 0;
-            uint64_t n_ovf = 0;
-            mtb_status s2 = dev_join(c, ix, d_s, nk, nullptr, 0, nullptr, &n_ovf, &sa, low_bits);
-            if (s2 == MTB_ERR_CAPACITY) {                              /* some read's tail overran: larger tails */
-                c->lslot_tf_start = 4;
-                if (c->opt.lslot_verbose) fprintf(stderr, "mtb: long-read slot path: %llu matches beyond the tails at tail factor %u/4\n", (unsigned long long)n_ovf, tf);
-                continue;
-            }
-            if (s2 != MTB_OK) return s2;
-            HIPCHK(hipEventRecord(c->ev[3], st));
-            STCHK(ensure(c, "matches", n_slots, &d_m));
-            HIPCHK(hipMemsetAsync(c->d_scal + 2, 0, 16, st));         /* [2] reads beyond the LDS tables, [3] matches of the range (incl. the dropped lonely ones) */
-            unsigned long long *d_work = (unsigned long long *)(c->d_xscal + 7);
-            HIPCHK(hipMemsetAsync(d_work, 0, 8, st));
-            { KTimer kt(c, MTB_K_SEGSORT);
-              hipLaunchKernelGGL(k_seg_order, dim3((uint32_t)std::min<uint64_t>(n_reads, 256ull * 2)), dim3(MTB_SO_NT), 0, st, (const mtb_slot16 *)d_segm, (const uint64_t *)d_rb,
-                                 (const uint32_t *)d_dcnt, (const uint32_t *)d_rc, tf, n_reads, d_m, d_live, (uint32_t *)(c->d_scal + 2), d_fail, d_work,
-                                 (unsigned long long *)(c->d_scal + 3)); }
-            HIPCHK(hipGetLastError());
-#ifdef MTB_SO_PHASE_CYCLES
-            {   HIPCHK(hipStreamSynchronize(st));
-                unsigned long long h[8], z[8] = {0};
-                HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(mtb_so_cycles), sizeof(h)));
-                HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(mtb_so_cycles), z, sizeof(z)));
-                static const char *nm[8] = {"claim + clear", "pass 1 (bits)", "pass 2 (counts, tail keys)", "single-match species", "tail sort", "species sort + offsets", "scatter pass", "tail pass"};
-                unsigned long long tot = 0; for (int k = 0; k < 8; k++) tot += h[k];
-                fprintf(stderr, "k_seg_order phases (%llu reads):", (unsigned long long)n_reads);
-                for (int k = 0; k < 8; k++) fprintf(stderr, " %s %.1f %%;", nm[k], tot ? 100.0 * (double)h[k] / (double)tot : 0.0);
-                fprintf(stderr, "\n");
-            }
-#endif
-            uint64_t sc2[2] = {0, 0};
-            STCHK(d2h(c, sc2, c->d_scal + 2, 16));
-            if (c->opt.lslot_verbose) fprintf(stderr, "mtb: long-read slot path: %llu reads, tail factor %u/4, %llu slots, %llu matches, %llu reads beyond the LDS tables (sorted the general way)\n",
-                                                     (unsigned long long)n_reads, tf, (unsigned long long)n_slots, (unsigned long long)sc2[1], (unsigned long long)(sc2[0] & 0xFFFFFFFFull));
-            const uint32_t n_failed = (uint32_t)(sc2[0] & 0xFFFFFFFFull);
-            /* reads beyond k_seg_order's LDS tables: their live slots -> exact segments, sorted the general way */
-            mtb_match *d_big = nullptr; uint64_t *d_bigstart = nullptr; uint32_t big_max = 0; uint64_t big_total = 0;
-            if (n_failed) {
-                uint32_t *d_bigcnt; mtb_match *d_scr; uint64_t mx = 0;
-                STCHK(ensure(c, "bigcnt", n_failed, &d_bigcnt)); STCHK(ensure(c, "bigstart", (uint64_t)n_failed + 1, &d_bigstart));
-                HIPCHK(hipMemsetAsync(c->d_scal + 4, 0, 8, st));
-                hipLaunchKernelGGL(k_lbig_count, dim3(std::min<uint32_t>(n_failed, 4096)), dim3(64), 0, st, (const mtb_slot16 *)d_segm, (const uint64_t *)d_rb, (const uint32_t *)d_dcnt,
-                                   (const uint32_t *)d_rc, tf, (const uint32_t *)d_fail, n_failed, d_bigcnt, (uint32_t *)(c->d_scal + 4));
-                scan_launch<uint32_t, uint64_t, false>(st, d_bigcnt, n_failed, true, d_bigstart, d_ws2);
-                STCHK(d2h(c, &big_total, d_bigstart + n_failed, 8));
-                STCHK(d2h(c, &mx, c->d_scal + 4, 8));
-                big_max = (uint32_t)mx;
-                STCHK(ensure(c, "bigm", big_total, &d_big)); STCHK(ensure(c, "jtemp", big_total, &d_scr));
-                hipLaunchKernelGGL(k_lbig_copy, dim3(std::min<uint32_t>(n_failed, 4096)), dim3(64), 0, st, (const mtb_slot16 *)d_segm, (const uint64_t *)d_rb, (const uint32_t *)d_dcnt,
-                                   (const uint32_t *)d_rc, tf, (const uint32_t *)d_fail, n_failed, (const uint64_t *)d_bigstart, d_big);
-                const size_t lds = (size_t)MTB_SEGLDS_CHUNK * 14;
-                HIPCHK(hipFuncSetAttribute((const void *)k_segsort_lds<mtb_match>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                { KTimer kt(c, MTB_K_SEGSORT);
-                  hipLaunchKernelGGL((k_segsort_lds<mtb_match>), dim3(std::min<uint32_t>(n_failed, 2048)), dim3(MTB_SEGLDS_THREADS), lds, st, d_big, (const uint64_t *)d_bigstart,
-                                     (const uint32_t *)nullptr, (const uint32_t *)(c->d_scal + 2), d_scr); }
-                HIPCHK(hipGetLastError());
-            }
-            HIPCHK(hipEventRecord(c->ev[4], st));
-            HIPCHK(hipEventRecord(c->ev[5], st));
-            STCHK(dev_score_long(c, ix, p, n_reads, d_ql, d_ql2, max_len, d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, n_taxcnt, tc_base, d_m, d_rb, max_q + mtb_lslot_tail(max_q, tf), d_live));
-            uint64_t n_generic = 0;
-            if (n_failed) {
-                STCHK(d2h(c, &n_generic, c->d_scal + 6, 8));        /* reads the first launch left to the generic kernel */
-                uint64_t n_tc2 = 0;
-                STCHK(dev_score_long(c, ix, p, n_reads, d_ql, d_ql2, max_len, d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, &n_tc2, tc_base, d_big, d_bigstart, big_max, nullptr, d_fail, n_failed));
-                uint64_t g2 = 0;
-                STCHK(d2h(c, &g2, c->d_scal + 6, 8));
-                n_generic = (n_generic & 0xFFFFFFFFull) + (g2 & 0xFFFFFFFFull);
-                STCHK(h2d(c, c->d_scal + 6, &n_generic, 8));
-            }
-            nm = sc2[1] + big_total;
-            done = true;
-        }
-        if (!done) {
-            /* redo this range without ordinal slots (tags stripped by a fresh extraction) */
-            c->no_lslot = true;
-            mtb_status s3 = classify_one(c, ix, p, d_bases, d_offs, d_bases2, d_offs2, n_reads, n_bases_total, d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, n_taxcnt, tc_base);
-            c->no_lslot = false;
-            return s3;
-        }
+        STCHK(score_long_slots(c, ix, p, n_reads, lens, q, out, n_taxcnt, &nm, &done));
+        if (!done) { *redo_exact = true; return MTB_OK; }
     } else {
         /* ---- long reads: exact segments (temp buffer, per-read counters, scan, regroup) ---- */
-        mtb_match *d_tmp;
-        DevBuf &jb = c->bufs["jtemp"];
-        uint64_t cap = std::max<uint64_t>(jb.cap / sizeof(mtb_match), nk + nk / 2 + 1024);
+        MatchList ml; ml.d_read_cnt = d_rc;
+        ml.cap = std::max<uint64_t>(buf_cap(c, "jtemp") / sizeof(mtb_match), q.nk + q.nk / 2 + 1024);
         for (int attempt = 0; attempt < 3; attempt++) {
-            STCHK(ensure(c, "jtemp", cap, &d_tmp));
-            mtb_status s2 = dev_join(c, ix, d_s, nk, d_tmp, cap, d_rc, &nm, nullptr, low_bits);
+            STCHK(ensure(c, "jtemp", ml.cap, &ml.d_out));
+            mtb_status s2 = dev_join(c, ix, q.d_s, q.nk, ml, &nm, /* no slot segments */ nullptr, q.low_bits);
             if (s2 == MTB_OK) break;
             if (s2 != MTB_ERR_CAPACITY || attempt == 2) return s2;
-            cap = nm + nm / 16 + 1024;                     /* the reference's retry (Classifier.cpp:127-131) with the exact size */
+            ml.cap = nm + nm / 16 + 1024;                     /* the reference's retry (Classifier.cpp:127-131) with the exact size */
             HIPCHK(hipMemsetAsync(d_rc, 0, n_reads * 4, st));
         }
         HIPCHK(hipEventRecord(c->ev[3], st));
-        STCHK(score_join_order(c, ix, p, d_tmp, nm, n_reads, d_rc, d_ql, d_ql2, max_len, d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, n_taxcnt, tc_base));
+        STCHK(score_join_order(c, ix, p, ml.d_out, nm, n_reads, d_rc, lens, out, n_taxcnt));
     }
     HIPCHK(hipEventRecord(c->ev[6], st));
     HIPCHK(hipEventSynchronize(c->ev[6]));
     mtb_batch_stats &S = c->stats;
-    HIPCHK(hipEventElapsedTime(&S.ms_extract, c->ev[0], c->ev[1]));
-    HIPCHK(hipEventElapsedTime(&S.ms_sort, c->ev[1], c->ev[2]));
-    HIPCHK(hipEventElapsedTime(&S.ms_join, c->ev[2], c->ev[3]));
-    HIPCHK(hipEventElapsedTime(&S.ms_regroup, c->ev[3], c->ev[4]));
-    HIPCHK(hipEventElapsedTime(&S.ms_segsort, c->ev[4], c->ev[5]));
-    HIPCHK(hipEventElapsedTime(&S.ms_score, c->ev[5], c->ev[6]));
+    float *const stage_ms[6] = {&S.ms_extract, &S.ms_sort, &S.ms_join, &S.ms_regroup, &S.ms_segsort, &S.ms_score};
+    for (int k = 0; k < 6; k++) HIPCHK(hipEventElapsedTime(stage_ms[k], c->ev[k], c->ev[k + 1]));
     HIPCHK(hipEventElapsedTime(&S.ms_total, c->ev[0], c->ev[6]));
     collect_kernel_times(c);
-    S.n_reads = n_reads; S.n_bases = n_bases_exact; S.n_kmers = nk_real; S.n_matches = nm; S.n_targets = ix->T;
-    if (c->fast_used) { uint64_t ns = 0; STCHK(d2h(c, &ns, c->d_scal + 6, 8)); S.n_generic_reads = ns & 0xFFFFFFFFull; c->fast_used = false; }
-    else S.n_generic_reads = n_reads;
+    S.n_reads = n_reads; S.n_bases = ex.n_bases; S.n_kmers = ex.nk_real; S.n_matches = nm; S.n_targets = ix->T;
+    STCHK(take_generic_reads(c, n_reads, &S.n_generic_reads));
     S.n_slot_reads = (fixed || lslot) ? n_reads : 0;
     if (fixed) { S.n_deferred_reads = c->many_stats[0]; S.n_many_reads = c->many_stats[1]; S.n_many_matches = c->many_stats[2]; S.n_many_kept = c->many_stats[3]; }
     return MTB_OK;
+}
+static mtb_status classify_one(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const Reads &rd, const ResultSink &out, uint64_t *n_taxcnt) {
+    bool redo_exact = false;
+    STCHK(classify_attempt(c, ix, p, rd, out, n_taxcnt, /* long_slots */ true, &redo_exact));
+    /* the long-read slot ranges overflowed: this range again without ordinal slots (tags stripped by a fresh extraction), on exact segments */
+    return redo_exact ? classify_attempt(c, ix, p, rd, out, n_taxcnt, /* long_slots */ false, &redo_exact) : MTB_OK;
 }
 
 static void merge_stats(mtb_batch_stats &S, const mtb_batch_stats &L) {
@@ -2653,10 +2664,8 @@ static void merge_stats(mtb_batch_stats &S, const mtb_batch_stats &L) {
  * is re-measured on every sub-batch.  The batch is cut into contiguous read ranges of equal size that fit; a range that
  * still runs out of memory is halved and redone.  Results land at their final places (d_results + lo, taxcnt slots
  * appended), so the caller sees one batch. */
-static mtb_status classify_budgeted(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const char *d_bases, const uint64_t *d_offs,
-                                    const char *d_bases2, const uint64_t *d_offs2, uint64_t n_reads, uint64_t n_bases_total,
-                                    mtb_result *d_results, int32_t *d_taxcnt_tax, uint32_t *d_taxcnt_cnt, uint64_t taxcnt_cap,
-                                    uint64_t *n_taxcnt, uint64_t tc_base0) {
+static mtb_status classify_budgeted(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const Reads &rd, uint64_t n_bases_total, const ResultSink &out, uint64_t *n_taxcnt) {
+    const uint64_t n_reads = rd.n_reads, taxcnt_cap = out.tc_cap;
     HIPCHK(hipSetDevice(c->device));
     *n_taxcnt = 0;
     c->last_sub_batches = 0; c->last_scratch_bytes = 0;
@@ -2667,7 +2676,7 @@ static mtb_status classify_budgeted(mtb_ctx *c, mtb_index *ix, const mtb_params 
     }
     size_t fr = 0, tot = 0;
     HIPCHK(hipMemGetInfo(&fr, &tot));
-    const size_t held = held_bytes(c);
+    const size_t held = held_bytes(c, BUF_FIXED);
     uint64_t budget = c->ws_limit ? c->ws_limit : (uint64_t)fr + held;
     if (!c->ws_limit) budget -= std::min<uint64_t>(budget / 16, 4ull << 30);          /* allocator granularity, kernel scratch, other users of the device */
     if (p->seq_mode == 3 && !c->ws_limit) budget -= std::min<uint64_t>(budget / 4, MTB_SLAB_POOL_MAX);     /* the slab pool of the large-segment scorer does not scale with the batch */
@@ -2694,9 +2703,8 @@ static mtb_status classify_budgeted(mtb_ctx *c, mtb_index *ix, const mtb_params 
         uint64_t n_tc = 0;
         mtb_status st;
         for (;;) {
-            st = classify_one(c, ix, p, d_bases, d_offs + lo, d_bases2, d_offs2 ? d_offs2 + lo : nullptr, cnt,
-                              (uint64_t)(mean_len * (double)cnt), d_results + lo, d_taxcnt_tax + tc_used, d_taxcnt_cnt + tc_used,
-                              taxcnt_cap - std::min(taxcnt_cap, tc_used), &n_tc, tc_base0 + tc_used);
+            st = classify_one(c, ix, p, rd.range(lo, cnt),
+                              ResultSink{out.d_res + lo, out.d_tc_tax + tc_used, out.d_tc_cnt + tc_used, taxcnt_cap - std::min(taxcnt_cap, tc_used), out.tc_base + tc_used}, &n_tc);
             if (st != MTB_ERR_OOM || cnt <= 1024) break;
             /* the estimate was too optimistic for this range: give the memory back, halve, redo */
             HIPCHK(hipStreamSynchronize(c->stream));
@@ -2714,7 +2722,7 @@ static mtb_status classify_budgeted(mtb_ctx *c, mtb_index *ix, const mtb_params 
         /* the buffers only grow: what they hold belongs to the largest sub-batch they have seen, not to this one (dividing by a
          * smaller one inflates the figure, more sub-batches follow, and the next measurement is worse still) */
         c->ws_max_sub_bases = std::max<uint64_t>(c->ws_max_sub_bases, c->stats.n_bases);
-        if (c->ws_max_sub_bases) c->ws_per_base = (double)scaling_bytes(c) / (double)c->ws_max_sub_bases;
+        if (c->ws_max_sub_bases) c->ws_per_base = (double)held_bytes(c, BUF_WORK) / (double)c->ws_max_sub_bases;
         if (c->opt.host_timing) {
             std::lock_guard<std::mutex> lk(c->bufs_mu);
             fprintf(stderr, "mtb budget: sub-batch of %llu reads (%llu bases) done; buffers (GiB):", (unsigned long long)cnt, (unsigned long long)c->stats.n_bases);
@@ -2739,8 +2747,7 @@ mtb_status mtb_classify_batch_device(mtb_ctx *c, mtb_index *ix, const mtb_params
     if (!c || !ix || !p || !n_taxcnt) return fail(MTB_ERR_ARG, "NULL argument");
     const size_t L = c->lanes.size();
     if (L < 2 || n_reads < 4096 * L)
-        return classify_budgeted(c, ix, p, d_bases, d_offs, d_bases2, d_offs2, n_reads, n_bases_total, d_results, d_taxcnt_tax, d_taxcnt_cnt,
-                                 taxcnt_cap, n_taxcnt, 0);
+        return classify_budgeted(c, ix, p, Reads{d_bases, d_offs, d_bases2, d_offs2, n_reads}, n_bases_total, ResultSink{d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, /* tc_base */ 0}, n_taxcnt);
     /* L contiguous read ranges, one host thread + one non-blocking stream each */
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));          /* inputs produced on the caller's stream are complete */
@@ -2765,9 +2772,8 @@ mtb_status mtb_classify_batch_device(mtb_ctx *c, mtb_index *ix, const mtb_params
             for (size_t k = i; k < NC; k += L) {
                 uint64_t lo = n_reads * k / NC, hi = n_reads * (k + 1) / NC;
                 uint64_t n_tc = 0;
-                mtb_status s = classify_one(l, ix, p, d_bases, d_offs + lo, d_bases2, d_offs2 ? d_offs2 + lo : nullptr, hi - lo,
-                                            n_bases_total * (hi - lo) / n_reads, d_results + lo, d_taxcnt_tax + tc_share * k,
-                                            d_taxcnt_cnt + tc_share * k, tc_share, &n_tc, tc_share * k);
+                mtb_status s = classify_one(l, ix, p, Reads{d_bases, d_offs, d_bases2, d_offs2, n_reads}.range(lo, hi - lo),
+                                            ResultSink{d_results + lo, d_taxcnt_tax + tc_share * k, d_taxcnt_cnt + tc_share * k, tc_share, tc_share * k}, &n_tc);
                 ntc[i] = std::max(ntc[i], n_tc * NC / L);
                 if (s != MTB_OK) { st[i] = s; errs[i] = g_err; break; }
                 merge_stats(lane_stats[i], l->stats);
@@ -2805,7 +2811,7 @@ mtb_status mtb_classify_batch(mtb_ctx *c, mtb_index *ix, const mtb_params *p, co
     mtb_result *d_res; int32_t *d_tt; uint32_t *d_tc;
     /* one stream: the lists come back packed, the device arrays are sized here and taxcnt_cap only bounds what the host receives */
     const uint64_t dcap = c->lanes.size() < 2 ? std::max<uint64_t>(taxcnt_cap, taxcnt_device_slots(p, n_reads, nb)) : taxcnt_cap;
-    STCHK(ensure(c, "results", n_reads, &d_res)); STCHK(ensure(c, "tctax", dcap, &d_tt)); STCHK(ensure(c, "tccnt", dcap, &d_tc));
+    STCHK(ensure(c, res_name(RES_ROWS, 0), n_reads, &d_res, BUF_IO)); STCHK(ensure(c, "tctax", dcap, &d_tt, BUF_IO)); STCHK(ensure(c, "tccnt", dcap, &d_tc, BUF_IO));
     mtb_status st = mtb_classify_batch_device(c, ix, p, d_b, d_o, d_b2, d_o2, n_reads, nb, d_res, d_tt, d_tc, dcap, n_taxcnt);
     if (st != MTB_OK) return st;
     if (c->lanes.size() < 2 && *n_taxcnt) return download_packed(c, d_res, d_tt, d_tc, n_reads, results, taxcnt_tax, taxcnt_cnt, n_taxcnt, taxcnt_cap);
@@ -2831,7 +2837,7 @@ static uint64_t packed_slots(const uint32_t *lens, uint64_t n_reads) {
 static mtb_status copy_packed(mtb_ctx *c, const char *tag, int set, hipStream_t on, const uint8_t *packed2, const uint8_t *nmask, const uint32_t *lens,
                               uint64_t n_reads, uint64_t slots, uint8_t **d_p2, uint8_t **d_nm, uint32_t **d_len) {
     const std::string t = std::string(tag) + (set ? "#1" : "#0");
-    STCHK(ensure(c, ("pk2" + t).c_str(), slots * 2 + 8, d_p2)); STCHK(ensure(c, ("pkm" + t).c_str(), slots + 8, d_nm)); STCHK(ensure(c, ("pklen" + t).c_str(), n_reads, d_len));
+    STCHK(ensure(c, ("pk2" + t).c_str(), slots * 2 + 8, d_p2, BUF_IO)); STCHK(ensure(c, ("pkm" + t).c_str(), slots + 8, d_nm, BUF_IO)); STCHK(ensure(c, ("pklen" + t).c_str(), n_reads, d_len, BUF_IO));
     HIPCHK(hipMemcpyAsync(*d_p2, packed2, slots * 2, hipMemcpyHostToDevice, on));
     HIPCHK(hipMemcpyAsync(*d_nm, nmask, slots, hipMemcpyHostToDevice, on));
     HIPCHK(hipMemcpyAsync(*d_len, lens, n_reads * 4, hipMemcpyHostToDevice, on));
@@ -2844,16 +2850,16 @@ static mtb_status upload_packed(mtb_ctx *c, const char *tag, int set, bool prefe
     uint8_t *d_p2, *d_nm; uint32_t *d_len, *d_sl; uint64_t *d_so, *d_ws;
     if (prefetched) {
         const std::string ts = t + (set ? "#1" : "#0");
-        d_p2 = (uint8_t *)c->bufs["pk2" + ts].p; d_nm = (uint8_t *)c->bufs["pkm" + ts].p; d_len = (uint32_t *)c->bufs["pklen" + ts].p;
+        d_p2 = (uint8_t *)buf_get(c, "pk2" + ts).p; d_nm = (uint8_t *)buf_get(c, "pkm" + ts).p; d_len = (uint32_t *)buf_get(c, "pklen" + ts).p;
     } else STCHK(copy_packed(c, tag, set, c->stream, packed2, nmask, lens, n_reads, packed_slots(lens, n_reads), &d_p2, &d_nm, &d_len));
-    STCHK(ensure(c, ("pksl" + t).c_str(), n_reads, &d_sl)); STCHK(ensure(c, ("pkso" + t).c_str(), n_reads + 1, &d_so));
-    STCHK(ensure(c, ("offs" + t).c_str(), n_reads + 1, d_offs)); STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws));
+    STCHK(ensure(c, ("pksl" + t).c_str(), n_reads, &d_sl, BUF_IO)); STCHK(ensure(c, ("pkso" + t).c_str(), n_reads + 1, &d_so, BUF_IO));
+    STCHK(ensure(c, ("offs" + t).c_str(), n_reads + 1, d_offs, BUF_IO)); STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws));
     scan_launch<uint32_t, uint64_t, false>(c->stream, d_len, n_reads, true, *d_offs, d_ws);
     hipLaunchKernelGGL(k_pack_slots, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, c->stream, (const uint32_t *)d_len, n_reads, d_sl);
     scan_launch<uint32_t, uint64_t, false>(c->stream, d_sl, n_reads, true, d_so, d_ws);
     uint64_t nb = 0;
     STCHK(d2h(c, &nb, *d_offs + n_reads, 8));
-    STCHK(ensure(c, ("bases" + t).c_str(), nb + 8, d_bases));
+    STCHK(ensure(c, ("bases" + t).c_str(), nb + 8, d_bases, BUF_IO));
     hipLaunchKernelGGL(k_unpack_reads, dim3((uint32_t)std::min<uint64_t>(n_reads, 256ull * 64)), dim3(64), 0, c->stream, (const uint8_t *)d_p2, (const uint8_t *)d_nm,
                        (const uint64_t *)*d_offs, (const uint64_t *)d_so, n_reads, *d_bases);
     HIPCHK(hipGetLastError());
@@ -2911,7 +2917,7 @@ static mtb_status classify_packed_impl(mtb_ctx *c, mtb_index *ix, const mtb_para
     if (c->unpacked[set]) { HIPCHK(hipEventRecord(c->unpacked[set], c->stream)); c->unpacked_rec[set] = true; }      /* the set may be overwritten by a prefetch from here on (stream order) */
     mtb_result *d_res; int32_t *d_tt; uint32_t *d_tc;
     const uint64_t dcap = c->lanes.size() < 2 ? std::max<uint64_t>(taxcnt_cap, taxcnt_device_slots(p, n_reads, nb + nb2)) : taxcnt_cap;     /* (as in mtb_classify_batch) */
-    STCHK(ensure(c, rset == 1 ? "resultsb" : "results", n_reads, &d_res)); STCHK(ensure(c, "tctax", dcap, &d_tt)); STCHK(ensure(c, "tccnt", dcap, &d_tc));
+    STCHK(ensure(c, res_name(RES_ROWS, rset), n_reads, &d_res, BUF_IO)); STCHK(ensure(c, "tctax", dcap, &d_tt, BUF_IO)); STCHK(ensure(c, "tccnt", dcap, &d_tc, BUF_IO));
     if (timing) HIPCHK(hipStreamSynchronize(c->stream));
     const double t1 = now();
     mtb_status st = mtb_classify_batch_device(c, ix, p, d_b, d_o, d_b2, d_o2, n_reads, nb + nb2, d_res, d_tt, d_tc, dcap, n_taxcnt);
@@ -3076,19 +3082,20 @@ mtb_status mtb_part_extract(mtb_ctx *c, const mtb_params *p, const char *d_bases
     if (n_reads == 0) return MTB_OK;
     int32_t *d_ql, *d_ql2;
     STCHK(ensure(c, "qlen", n_reads, &d_ql)); STCHK(ensure(c, "qlen2", n_reads, &d_ql2));
-    mtb_kmer *d_k, *d_s; uint64_t nk; uint32_t max_len = 0;
+    mtb_kmer *d_s; Extracted ex; const Reads rd{d_bases, d_offs, d_bases2, d_offs2, n_reads};
     if (part_starts && p->seq_mode != 3 && !c->opt.part_exact) {
         /* the product path of short reads: single-pass extraction with ordinals, the sort on the leading amino-acid letters only (it is
          * there for the locality of the owners' directory joins) -- so a run is cut at PREFIX granularity and the metamers that share
          * their prefix with a bound go to both neighbours: a query finds candidates only in the range that holds its amino-acid
          * group (no group straddles a cut), the other owner emits nothing for it */
-        uint32_t max_q = 0; uint64_t nk_real = 0; uint16_t *d_dig = nullptr;
         const bool aa6 = p->kmer_format == 2;
-        STCHK(dev_extract(c, p, d_bases, d_offs, d_bases2, d_offs2, n_reads, &d_k, &nk, d_ql, d_ql2, &max_len, true, 0, &nk_real, true, &max_q, aa6 ? &d_dig : nullptr));
-        if (max_len + 3 < MTB_SLOT_MAX_POS && max_q <= 384) {
+        ExtractOpts tagged; tagged.single_pass = true; tagged.tag_ordinals = true; tagged.want_digits = aa6;
+        STCHK(dev_extract(c, p, rd, d_ql, d_ql2, tagged, &ex));
+        const uint64_t nk = ex.nk;
+        if (ex.max_len + 3 < MTB_SLOT_MAX_POS && ex.max_q <= 384) {
             const int low_bits = aa6 ? 34 : 32;
-            STCHK(dev_sort(c, d_k, nk, aa6 ? MTB_SORT_AA6 : 32, &d_s, d_dig));
-            c->part_max_len = max_len; c->part_mode = 1; c->part_max_q = max_q; c->part_nk_real = nk_real;
+            STCHK(dev_sort(c, ex.d_k, ex.nk, aa6 ? MTB_SORT_AA6 : 32, &d_s, ex.d_dig, /* all six letters */ 34));
+            c->part_max_len = ex.max_len; c->part_mode = 1; c->part_max_q = ex.max_q; c->part_nk_real = ex.nk_real;
             std::vector<uint64_t> key(2 * n_parts), pos(2 * n_parts);
             for (uint32_t q = 0; q < n_parts; q++) {
                 const uint64_t pre = bounds[q] >> low_bits;
@@ -3105,10 +3112,11 @@ mtb_status mtb_part_extract(mtb_ctx *c, const mtb_params *p, const char *d_bases
             return MTB_OK;
         }
     }
-    STCHK(dev_extract(c, p, d_bases, d_offs, d_bases2, d_offs2, n_reads, &d_k, &nk, d_ql, d_ql2, &max_len));
+    STCHK(dev_extract(c, p, rd, d_ql, d_ql2, /* two passes, untagged: exact order */ ExtractOpts(), &ex));
+    const uint64_t nk = ex.nk;
     /* partition boundaries are amino-acid-part boundaries (bit 24), finer than the 32-bit tiles of the fused path: 5 passes */
-    STCHK(dev_sort(c, d_k, nk, 24, &d_s));
-    c->part_max_len = max_len;
+    STCHK(dev_sort(c, ex.d_k, ex.nk, 24, &d_s, /* binary passes: no digit array, no letter pairs */ nullptr, 0));
+    c->part_max_len = ex.max_len;
     std::vector<uint64_t> pos(n_parts);
     if (nk) STCHK(lower_bounds(c, (const uint64_t *)d_s, nk, 2, bounds, n_parts, pos.data()));
     for (uint32_t q = 0; q < n_parts; q++) { uint64_t hi = q + 1 < n_parts ? pos[q + 1] : nk; part_counts[q] = hi >= pos[q] ? hi - pos[q] : 0; if (part_starts) part_starts[q] = pos[q]; }
@@ -3127,14 +3135,14 @@ mtb_status mtb_part_join(mtb_ctx *c, mtb_index *ix, const mtb_kmer *d_kmers, uin
          * batch) and says in `pad` whether it is the query's first match */
         JoinSegArgs sa; memset(&sa, 0, sizeof(sa));
         sa.list = 1; sa.ovf = d_out; sa.ovf_cap = cap;
-        return dev_join(c, ix, d_kmers, n, nullptr, 0, nullptr, count, &sa);
+        return dev_join(c, ix, d_kmers, n, MatchList(), count, &sa, /* sort_low_bits: no window form for dense lists */ 32);
     }
     /* no directory over this range (MTB_NO_DIR, no room, a letter >= 21, a tiny range): the bisection join.  The runs of a slot-mode
      * batch are ordered on the leading amino-acid letters only (bits [34, 64) for kmer_format 2, mtb_part_extract), and k_join_bounds
      * derives a tile's target window from its first and last query under exactly that assumption -- so the sender's granularity is
      * passed on (the exact-order runs of the other modes are ordered on those bits too).  Records leave with pad = 0: the home rank
      * places them through the tails / the overflow list, which is slower but exact. */
-    return dev_join(c, ix, d_kmers, n, d_out, cap, nullptr, count, nullptr, ix->params.kmer_format == 2 ? 34 : 32);
+    return dev_join(c, ix, d_kmers, n, MatchList{d_out, cap}, count, /* no slot segments */ nullptr, ix->params.kmer_format == 2 ? 34 : 32);
 }
 
 mtb_status mtb_part_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, mtb_match *d_matches, uint64_t n_matches, uint64_t n_reads,
@@ -3148,43 +3156,37 @@ mtb_status mtb_part_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, mtb_ma
     int32_t *d_ql, *d_ql2; uint32_t *d_rc; mtb_result *d_res; int32_t *d_tt; uint32_t *d_tc;
     STCHK(ensure(c, "qlen", n_reads, &d_ql)); STCHK(ensure(c, "qlen2", n_reads, &d_ql2));
     STCHK(ensure(c, "readcnt", n_reads, &d_rc));
-    STCHK(ensure(c, "results", n_reads, &d_res)); STCHK(ensure(c, "tctax", taxcnt_cap, &d_tt)); STCHK(ensure(c, "tccnt", taxcnt_cap, &d_tc));
+    STCHK(ensure(c, res_name(RES_ROWS, 0), n_reads, &d_res, BUF_IO)); STCHK(ensure(c, "tctax", taxcnt_cap, &d_tt, BUF_IO)); STCHK(ensure(c, "tccnt", taxcnt_cap, &d_tc, BUF_IO));
+    const ResultSink sink{d_res, d_tt, d_tc, taxcnt_cap, /* tc_base */ 0};
     if (c->part_mode == 1) {
         /* slot mode: the matches are placed into this rank's slot segments by their ordinal (what the fused join does at once),
          * then the slot scorers run */
-        hipStream_t st = c->stream;
-        uint32_t direct, stride;
-        slot_geometry(c, c->part_max_q, &direct, &stride);
-        mtb_slot16 *d_segm; mtb_match *d_ovf; uint32_t epoch = 0; uint64_t n_ovf = 0;
-        STCHK(prepare_slots(c, n_reads, stride, &d_segm, &epoch));
-        DevBuf &ob = c->bufs["ovf"];
-        uint64_t ovf_cap = std::max<uint64_t>(ob.cap / sizeof(mtb_match), n_matches / 64 + 4096);
+        hipStream_t st = c->stream; SlotSegs sl;
+        STCHK(make_slots(c, n_reads, c->part_max_q, d_rc, &sl));
+        uint64_t ovf_cap = ovf_cap_first(c, n_matches);
         for (int attempt = 0; attempt < 3; attempt++) {
-            STCHK(ensure(c, "ovf", ovf_cap, &d_ovf));
+            STCHK(ensure(c, "ovf", ovf_cap, &sl.d_ovf));
             HIPCHK(hipMemsetAsync(d_rc, 0, n_reads * 4, st));
-            HIPCHK(hipMemsetAsync(c->d_scal, 0, 16, st));
+            HIPCHK(scal_clear(c, SC_JOIN_COUNT, 2));
             JoinSegArgs sa; memset(&sa, 0, sizeof(sa));
-            sa.seg = d_segm; sa.stride = stride; sa.direct = direct; sa.cursor = d_rc; sa.ovf = d_ovf; sa.ovf_cap = ovf_cap; sa.ovf_counter = (unsigned long long *)c->d_scal; sa.epoch = epoch;
-            if (n_matches) hipLaunchKernelGGL(k_slot_place, dim3((uint32_t)((n_matches + 255) / 256)), dim3(256), 0, st, (const mtb_match *)d_matches, n_matches, sa, n_reads, (uint32_t *)(c->d_scal + 1));
+            sa.seg = sl.d_segm; sa.stride = sl.stride; sa.direct = sl.direct; sa.cursor = d_rc; sa.ovf = sl.d_ovf; sa.ovf_cap = ovf_cap; sa.ovf_counter = scal<unsigned long long>(c, SC_JOIN_COUNT); sa.epoch = sl.epoch;
+            if (n_matches) hipLaunchKernelGGL(k_slot_place, dim3((uint32_t)((n_matches + 255) / 256)), dim3(256), 0, st, (const mtb_match *)d_matches, n_matches, sa, n_reads, scal<uint32_t>(c, SC_BAD_SEQ));
             HIPCHK(hipGetLastError());
-            uint64_t sc[2];
-            STCHK(d2h(c, sc, c->d_scal, 16));
+            uint64_t sc[2]; STCHK(d2h(c, sc, scal<uint64_t>(c, SC_JOIN_COUNT), 16));       /* ... and SC_BAD_SEQ */
             if (sc[1] & 0xFFFFFFFFull) return fail(MTB_ERR_ARG, "match records with a sequenceID outside 1..n_reads");
-            n_ovf = sc[0];
-            if (n_ovf <= ovf_cap) break;
+            sl.n_ovf = sc[0];
+            if (sl.n_ovf <= ovf_cap) break;
             if (attempt == 2) return fail(MTB_ERR_CAPACITY, "overflow list too small");
-            ovf_cap = n_ovf + n_ovf / 16 + 1024;          /* slots written by the failed attempt are rewritten identically */
+            ovf_cap = ovf_cap_regrown(sl.n_ovf);          /* slots written by the failed attempt are rewritten identically */
         }
-        uint64_t nm = 0;
-        memset(&c->stats, 0, sizeof(c->stats));
-        STCHK(score_fixed_slots(c, ix, p, n_reads, d_ql, d_ql2, c->part_max_len, c->part_nk_real, d_segm, d_rc, stride, direct, epoch, d_ovf, n_ovf,
-                                d_res, d_tt, d_tc, taxcnt_cap, n_taxcnt, 0, &nm));
+        uint64_t nm = 0; memset(&c->stats, 0, sizeof(c->stats));
+        STCHK(score_fixed_slots(c, ix, p, n_reads, ReadLens{d_ql, d_ql2, c->part_max_len}, c->part_nk_real, sl, sink, n_taxcnt, &nm));
         c->stats.n_reads = n_reads; c->stats.n_matches = nm; c->stats.n_slot_reads = n_reads; c->stats.n_kmers = c->part_nk_real;
-        if (c->fast_used) { uint64_t ns = 0; STCHK(d2h(c, &ns, c->d_scal + 6, 8)); c->stats.n_generic_reads = ns & 0xFFFFFFFFull; c->fast_used = false; }
+        STCHK(take_generic_reads(c, /* left at 0 when nothing was listed */ 0, &c->stats.n_generic_reads));
         return download_packed(c, d_res, d_tt, d_tc, n_reads, results, taxcnt_tax, taxcnt_cnt, n_taxcnt);
     }
     STCHK(count_reads(c, d_matches, n_matches, n_reads, d_rc));
-    STCHK(score_join_order(c, ix, p, d_matches, n_matches, n_reads, d_rc, d_ql, d_ql2, c->part_max_len, d_res, d_tt, d_tc, taxcnt_cap, n_taxcnt, 0));
+    STCHK(score_join_order(c, ix, p, d_matches, n_matches, n_reads, d_rc, ReadLens{d_ql, d_ql2, c->part_max_len}, sink, n_taxcnt));
     return download_packed(c, d_res, d_tt, d_tc, n_reads, results, taxcnt_tax, taxcnt_cnt, n_taxcnt);
 }
 
@@ -3366,12 +3368,9 @@ mtb_status mtb_debug_fast_reasons(mtb_ctx *c, unsigned long long *out8) {
 mtb_status mtb_debug_move_buffer(mtb_ctx *c, const char *name, unsigned long long pad_bytes) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->stream));
-    auto it = c->bufs.find(name);
-    void *old = nullptr;
-    if (it != c->bufs.end()) { old = it->second.p; it->second.p = nullptr; it->second.cap = 0; }
     void *pad = nullptr;
     if (pad_bytes) { hipError_t e = hipMalloc(&pad, pad_bytes); if (e != hipSuccess) { (void)hipGetLastError(); pad = nullptr; } }   /* never freed: the process ends with the experiment */
-    if (old) { hipError_t e = hipFree(old); (void)e; }
+    release(c, name);             /* after the pad is in place */
     return MTB_OK;
 }
 #endif

@@ -4,7 +4,7 @@ buffer's clearing and placement, the long-read scorers, the fused amino-acid sor
 MTB_* switches that select among them (mtb_options.h: "none changes a result").  One oracle answer per synthetic world, reused for
 every switch setting on one context; every case compares bit for bit and asserts through mtb_batch_stats that its path ran.
 
-`slot_plan` mirrors the dispatch of mtb_api.hip (classify_one, slot_geometry, dev_score, score_fixed_slots) from the oracle's
+`slot_plan` mirrors the dispatch of mtb_api.hip (classify_attempt, slot_geometry, dev_score, score_fixed_slots) from the oracle's
 metamer counts, and every case asserts that it landed in the bucket its id names -- so the parametrisation cannot drift from the
 boundaries it is there to cover.  SWITCH_CASES lists which case covers which switch; test_abi.py checks it against mtb_options.h."""
 import os
@@ -84,7 +84,7 @@ def fast_bucket(stride, paired):
 
 
 def slot_plan(counts, qlen_total, paired, tail_min=0):
-    """classify_one's choices for a short-read batch from the per-read metamer counts and used lengths: slot path or not, the reads
+    """classify_attempt's choices for a short-read batch from the per-read metamer counts and used lengths: slot path or not, the reads
     routed around the slots, the slot geometry, the fast-scorer bucket and the generic k_score's LDS cap (score_fixed_slots)"""
     n = len(counts)
     off = (counts > SLOT_MAX_Q) | (qlen_total + 3 >= SLOT_MAX_POS)
