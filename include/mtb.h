@@ -463,6 +463,60 @@ mtb_status mtb_synth_index(mtb_ctx *, uint64_t seed, uint64_t n_filler, int32_t 
 mtb_status mtb_extract_targets(mtb_ctx *, const mtb_params *, const char *genome, uint64_t len,
                                uint64_t *values, uint64_t cap, uint64_t *count);
 
+/* ---- database build and merge -------------------------------------------
+ * Replaces the sort + filter of IndexCreator::createIndex (IndexCreator.cpp:343-373: SORT_PARALLEL with Kmer::compareTargetKmer,
+ * Kmer.h:77-87, then filterKmers<DB_CREATION>, IndexCreator.h:476-615) and mergeTargetFiles<DB_CREATION> (IndexCreator.h:323-472,
+ * what updateDB.cpp:138-142 calls): a builder collects (value, taxid) records on the device -- extracted from sequences, given by
+ * the caller, or taken from open databases -- and mtb_builder_finish turns their multiset into an index: with
+ * s = taxId2speciesId[taxid] (the table mtb_index_open builds, here from the union of the ids added, which is the new database's
+ * taxID_list), one entry per distinct (value, s) whose info is the LCA of the group's taxids (the canonical node: a group of one
+ * gives the merged.dmp target of its id), in (value, s) order.
+ * Gene prediction is NOT part of this: mtb_builder_add_sequences extracts every sequence in all six frames (long-read geometry),
+ * as the toy and benchmark databases are built, not the reference's Prodigal-guided extraction; a caller with CDS-restricted
+ * metamers passes them to mtb_builder_add_records.
+ * `params` fixes kmer_format, syncmer and smer_len of everything added.  Every taxid added must exist in the taxonomy (after
+ * merged.dmp aliasing): otherwise the call returns MTB_ERR_ARG, mtb_last_error() names the first offending id and the builder
+ * holds what it held before.  All pointers are host memory.
+ * Reduced_alphabet: mtb_params has no field for it, so mtb_builder_create can refuse it (MTB_ERR_UNSUPPORTED) only where it can
+ * see it: when `taxonomy_dir`/../db.parameters exists and says `Reduced_alphabet 1`, i.e. the taxonomy directory is the one
+ * inside such a database.  A taxonomy directory that merely sits beside a db.parameters of that kind is refused too: copy it.
+ * A reduced-alphabet OLD database never reaches mtb_builder_add_index, because mtb_index_open refuses to open it.
+ * Memory: the records are one device array of 16 B each that grows by half when full (allocate, copy, free), so while it grows
+ * both copies exist: up to 2.5 x the list, 40 B per record held, and MTB_ERR_OOM comes that much before HBM is full.  finish
+ * needs the list plus two sort buffers of the same size (48 B per record) plus the output.  Callers that know the total add the
+ * largest part first; each add_sequences call costs an upload, a two-pass extraction and a few stream synchronisations, so
+ * pass many sequences per call (mtb_build passes about 64 M bases at a time). */
+typedef struct mtb_builder mtb_builder;
+mtb_status mtb_builder_create(mtb_ctx *, const char *taxonomy_dir, const mtb_params *, mtb_builder **out);
+mtb_status mtb_builder_add_sequences(mtb_builder *, const char *bases, const uint64_t *offs,
+                                     const int32_t *taxids, uint64_t n_seqs);
+mtb_status mtb_builder_add_records(mtb_builder *, const uint64_t *values, const int32_t *taxids, uint64_t n);
+/* the (value, info & info_mask) pairs of a resident index of the same device (updateDB's old database; bit 31 of legacy
+ * databases is masked off as mergeTargetFiles does, IndexCreator.h:355, 400).  A sealed or packed index is brought to the flat
+ * state as for mtb_index_download and held there, as a join holds its state, until its entries are copied: classification
+ * against the same index from another thread waits or proceeds, never sees a half-read array.  MTB_ERR_ARG: a view, or
+ * kmer_format / syncmer / smer_len differ from the builder's. */
+mtb_status mtb_builder_add_index(mtb_builder *, mtb_index *);
+uint64_t   mtb_builder_num_records(const mtb_builder *);
+/* An ordinary owning index (flat state, directory built, skip_redundancy = 1) for mtb_classify_batch*, mtb_index_write,
+ * mtb_index_seal, mtb_index_clone, mtb_index_download; the builder is empty afterwards and may be reused.  MTB_ERR_ARG: no
+ * records, or 2^32 or more of them (the device sort's limit: build in parts and merge the parts).  The context's batch
+ * workspace is released on the way (the sort needs the room). */
+mtb_status mtb_builder_finish(mtb_builder *, mtb_index **out);
+void       mtb_builder_destroy(mtb_builder *);
+/* Device time of the last mtb_builder_finish by stage, and what it saw.  Part of the ABI on purpose, and small: it is the only
+ * way a caller (or a test) can tell that the wavefront tier of the reduce ran (n_long_groups: groups of more than 16 records),
+ * how far the dedup shrank the input (n_entries / n_records), and where the time of a build went, without a profiler;
+ * profiles/scripts/index_build_measure.py reads it.  The times come from events the builder owns (the context's batch
+ * statistics are not touched); all zero before the first finish. */
+enum { MTB_BUILD_KEYS = 0, MTB_BUILD_SORT_KEY = 1, MTB_BUILD_SORT_VALUE = 2, MTB_BUILD_HEADS_SCAN = 3, MTB_BUILD_REDUCE = 4,
+       MTB_BUILD_TOTAL = 5, MTB_BUILD_STAGES = 6 };
+typedef struct {
+    float    ms[MTB_BUILD_STAGES];
+    uint64_t n_records, n_entries, n_long_groups;     /* input records, output entries, groups a whole wavefront folded */
+} mtb_build_stats;
+mtb_status mtb_builder_last_finish_stats(const mtb_builder *, mtb_build_stats *out);
+
 #ifdef __cplusplus
 }
 #endif

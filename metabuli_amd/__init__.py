@@ -227,6 +227,12 @@ class Context:
                                     _p(rv), _p(rt), C.c_uint64(len(rv)), C.c_void_p(d_values), C.c_void_p(d_info), C.byref(n)))
         return n.value
 
+    def builder(self, taxonomy_dir, params):
+        """a database builder on this context's GPU (mtb_builder_create): collects (value, taxid) records, finish() -> Index"""
+        h = C.c_void_p()
+        _chk(self.L.mtb_builder_create(self.h, taxonomy_dir.encode(), C.byref(params), C.byref(h)))
+        return Builder(self, h)
+
     # ---- stages (host buffers) ----
     def extract(self, params, bases, offs, bases2=None, offs2=None, cap=None):
         n = len(offs) - 1
@@ -472,6 +478,64 @@ class Context:
         s = BatchStats()
         _chk(self.L.mtb_last_batch_stats(self.h, C.byref(s)))
         return s
+
+
+class BuildStats(C.Structure):
+    _fields_ = [("ms", C.c_float * 6), ("n_records", C.c_uint64), ("n_entries", C.c_uint64), ("n_long_groups", C.c_uint64)]
+
+
+BUILD_STAGES = ["keys", "sort_key", "sort_value", "heads_scan", "reduce", "total"]
+
+
+class Builder:
+    """Database build / merge on the device (mtb_builder_*): the sort and the per-species LCA dedup of the reference's `build` /
+    `updateDB`.  Sequences are extracted in all six frames (no gene prediction)."""
+
+    def __init__(self, ctx, h):
+        self.ctx = ctx
+        self.h = h
+
+    def add_sequences(self, bases, offs, taxids):
+        """sequences concatenated in `bases` with offs[n + 1]; taxids[i] = taxid of sequence i"""
+        b = np.ascontiguousarray(bases, dtype=np.uint8)
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        t = np.ascontiguousarray(taxids, dtype=np.int32)
+        assert len(o) == len(t) + 1
+        _chk(self.ctx.L.mtb_builder_add_sequences(self.h, _p(b), _p(o), _p(t), C.c_uint64(len(t))))
+
+    def add_records(self, values, taxids):
+        v = np.ascontiguousarray(values, dtype=np.uint64)
+        t = np.ascontiguousarray(taxids, dtype=np.int32)
+        assert len(v) == len(t)
+        _chk(self.ctx.L.mtb_builder_add_records(self.h, _p(v), _p(t), C.c_uint64(len(v))))
+
+    def add_index(self, index):
+        """the entries of an open database (updateDB's old database)"""
+        _chk(self.ctx.L.mtb_builder_add_index(self.h, index.h))
+
+    @property
+    def num_records(self):
+        self.ctx.L.mtb_builder_num_records.restype = C.c_uint64
+        return int(self.ctx.L.mtb_builder_num_records(self.h))
+
+    def finish(self):
+        """-> Index (flat, owning); the builder is empty afterwards and may be reused"""
+        h = C.c_void_p()
+        _chk(self.ctx.L.mtb_builder_finish(self.h, C.byref(h)))
+        return Index(self.ctx, h)
+
+    def last_finish_stats(self):
+        """device milliseconds of the last finish() by stage, and its record / entry / long-group counts"""
+        s = BuildStats()
+        _chk(self.ctx.L.mtb_builder_last_finish_stats(self.h, C.byref(s)))
+        d = dict(zip(BUILD_STAGES, [float(x) for x in s.ms]))
+        d.update(n_records=int(s.n_records), n_entries=int(s.n_entries), n_long_groups=int(s.n_long_groups))
+        return d
+
+    def close(self):
+        if self.h:
+            self.ctx.L.mtb_builder_destroy(self.h)
+            self.h = None
 
 
 class Index:

@@ -21,6 +21,7 @@
 #include "kernels_extract.h"
 #include "kernels_index.h"
 #include "kernels_join.h"
+#include "kernels_build.h"
 #include "kernels_dir.h"
 #include "kernels_scan.h"
 #include "kernels_score.h"
@@ -3546,6 +3547,258 @@ mtb_status mtb_extract_targets(mtb_ctx *c, const mtb_params *p, const char *geno
     *count = n;
     if (st != MTB_OK) return st;
     for (uint64_t i = 0; i < n; i++) values[i] = tmp[i].value;
+    return MTB_OK;
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------------------ */
+/* database build / merge (kernels_build.h)                            */
+/* ------------------------------------------------------------------ */
+struct mtb_builder {
+    mtb_ctx *ctx = nullptr;
+    mtb_params params;
+    mtbhost::Taxonomy tax;           /* loaded once; every index finish() returns starts from a copy */
+    int32_t *d_canon = nullptr;      /* canon[] alone: what mtb_tax_exists reads (add_index checks its ids on the device) */
+    mtb_kmer *d_rec = nullptr;       /* the records: {value, taxid in qinfo} */
+    uint64_t n = 0, cap = 0;
+    hipEvent_t ev[MTB_BUILD_STAGES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      /* stage boundaries of finish(): the builder's own, not the context's batch events */
+    float ms[MTB_BUILD_STAGES] = {0, 0, 0, 0, 0, 0};
+    uint64_t last_n = 0, last_groups = 0, last_long = 0;
+};
+
+/* room for `more` records behind the ones held (the list is copied when it grows) */
+static mtb_status builder_reserve(mtb_builder *b, uint64_t more) {
+    const uint64_t need = b->n + more;
+    if (need <= b->cap) return MTB_OK;
+    const uint64_t want = std::max<uint64_t>(need, b->cap + b->cap / 2);
+    mtb_kmer *p = nullptr;
+    hipError_t e = hipMalloc((void **)&p, want * sizeof(mtb_kmer));
+    uint64_t got = want;
+    if (e != hipSuccess && want > need) { (void)hipGetLastError(); got = need; e = hipMalloc((void **)&p, need * sizeof(mtb_kmer)); }
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(MTB_ERR_OOM, "not enough HBM for the builder's record list (" + std::to_string(need) + " records)"); }
+    if (b->n) {
+        hipError_t e2 = hipMemcpyAsync(p, b->d_rec, b->n * sizeof(mtb_kmer), hipMemcpyDeviceToDevice, b->ctx->stream);
+        if (e2 == hipSuccess) e2 = hipStreamSynchronize(b->ctx->stream);
+        if (e2 != hipSuccess) { hipError_t e3 = hipFree(p); (void)e3; return fail(MTB_ERR_DEVICE, std::string("builder: copy of the record list: ") + hipGetErrorString(e2)); }
+    }
+    if (b->d_rec) { hipError_t e3 = hipFree(b->d_rec); (void)e3; }
+    b->d_rec = p; b->cap = got;
+    return MTB_OK;
+}
+static mtb_status builder_check_taxids(const mtb_builder *b, const int32_t *taxids, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++)
+        if (b->tax.cn(taxids[i]) < 0) return fail(MTB_ERR_ARG, "taxid " + std::to_string(taxids[i]) + " is not in the taxonomy (nodes.dmp / merged.dmp)");
+    return MTB_OK;
+}
+static dim3 grid256(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
+
+extern "C" {
+
+mtb_status mtb_builder_create(mtb_ctx *c, const char *taxonomy_dir, const mtb_params *params, mtb_builder **out) {
+    if (!c || !taxonomy_dir || !params || !out) return fail(MTB_ERR_ARG, "NULL argument");
+    if (params->kmer_format != 1 && params->kmer_format != 2) return fail(MTB_ERR_UNSUPPORTED, "only kmer_format 1 and 2 are implemented");
+    if (params->syncmer && (params->smer_len < 1 || params->smer_len > 8)) return fail(MTB_ERR_ARG, "smer_len out of range");
+    HIPCHK(hipSetDevice(c->device));
+    {   /* Reduced_alphabet is a property of a database and mtb_params has no field for it: the one place a builder can meet it is a
+         * taxonomy directory that sits inside such a database (DB/taxonomy), whose DB/db.parameters says so (documented in mtb.h) */
+        mtb_params q = *params; int reduced_aa = 0;
+        mtbhost::load_db_parameters(std::string(taxonomy_dir) + "/..", &q, &reduced_aa);
+        if (reduced_aa) return fail(MTB_ERR_UNSUPPORTED, "Reduced_alphabet 1 is not implemented");
+    }
+    mtb_builder *b = new mtb_builder();
+    b->ctx = c; b->params = *params; b->params.skip_redundancy = 1;
+    std::string err;
+    if (!mtbhost::load_taxonomy(taxonomy_dir, &b->tax, &err)) { delete b; return fail(MTB_ERR_IO, err); }
+    const size_t nt = (size_t)b->tax.max_id + 1;
+    hipError_t e = hipMalloc((void **)&b->d_canon, nt * 4);
+    if (e != hipSuccess) { (void)hipGetLastError(); delete b; return fail(MTB_ERR_OOM, "not enough HBM for the builder's taxonomy table"); }
+    e = hipMemcpy(b->d_canon, b->tax.canon.data(), nt * 4, hipMemcpyHostToDevice);
+    for (int k = 0; k < MTB_BUILD_STAGES && e == hipSuccess; k++) e = hipEventCreate(&b->ev[k]);
+    if (e != hipSuccess) { (void)hipGetLastError(); mtb_builder_destroy(b); return fail(MTB_ERR_DEVICE, std::string("builder: taxonomy upload / events: ") + hipGetErrorString(e)); }
+    *out = b;
+    return MTB_OK;
+}
+
+void mtb_builder_destroy(mtb_builder *b) {
+    if (!b) return;
+    hipError_t e = hipSuccess;
+    if (b->d_rec) e = hipFree(b->d_rec);
+    if (b->d_canon) e = hipFree(b->d_canon);
+    for (int k = 0; k < MTB_BUILD_STAGES; k++) if (b->ev[k]) e = hipEventDestroy(b->ev[k]);
+    (void)e;
+    delete b;
+}
+
+uint64_t mtb_builder_num_records(const mtb_builder *b) { return b ? b->n : 0; }
+
+mtb_status mtb_builder_add_records(mtb_builder *b, const uint64_t *values, const int32_t *taxids, uint64_t n) {
+    if (!b || (n && (!values || !taxids))) return fail(MTB_ERR_ARG, "NULL argument");
+    if (n == 0) return MTB_OK;
+    mtb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    STCHK(builder_check_taxids(b, taxids, n));
+    STCHK(builder_reserve(b, n));
+    const uint64_t CHUNK = 1ull << 24;         /* staged through two small device arrays */
+    uint64_t *d_v; int32_t *d_t;
+    STCHK(ensure(c, "bvals", std::min(n, CHUNK), &d_v, BUF_IO)); STCHK(ensure(c, "btax", std::min(n, CHUNK), &d_t, BUF_IO));
+    for (uint64_t i0 = 0; i0 < n; i0 += CHUNK) {
+        const uint64_t m = std::min(CHUNK, n - i0);
+        HIPCHK(hipMemcpyAsync(d_v, values + i0, m * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(d_t, taxids + i0, m * 4, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_build_pack, grid256(m), dim3(256), 0, c->stream, (const uint64_t *)d_v, (const int32_t *)d_t, m, b->d_rec + b->n + i0);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (n > CHUNK) { release(c, "bvals"); release(c, "btax"); }
+    b->n += n;
+    return MTB_OK;
+}
+
+mtb_status mtb_builder_add_sequences(mtb_builder *b, const char *bases, const uint64_t *offs, const int32_t *taxids, uint64_t n_seqs) {
+    if (!b || (n_seqs && (!bases || !offs || !taxids))) return fail(MTB_ERR_ARG, "NULL argument");
+    if (n_seqs == 0) return MTB_OK;
+    mtb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    STCHK(builder_check_taxids(b, taxids, n_seqs));
+    /* the toy and bench databases' geometry: every sequence in all six frames, long-read mode (no gene prediction) */
+    mtb_params q = b->params; q.seq_mode = 3;
+    char *d_b, *d_b2; uint64_t *d_o, *d_o2; uint64_t nb;
+    STCHK(upload_reads(c, &q, bases, offs, nullptr, nullptr, n_seqs, &d_b, &d_o, &d_b2, &d_o2, &nb));
+    int32_t *d_ql, *d_ql2, *d_t;
+    STCHK(ensure(c, "qlen", n_seqs, &d_ql)); STCHK(ensure(c, "qlen2", n_seqs, &d_ql2)); STCHK(ensure(c, "btax", n_seqs, &d_t, BUF_IO));
+    STCHK(h2d(c, d_t, taxids, n_seqs * 4));
+    ExtractOpts two_pass; two_pass.want_max_len = false;
+    Extracted ex;
+    STCHK(dev_extract(c, &q, Reads{d_b, d_o, nullptr, nullptr, n_seqs}, d_ql, d_ql2, two_pass, &ex));
+    if (ex.nk == 0) return MTB_OK;
+    STCHK(builder_reserve(b, ex.nk));
+    hipLaunchKernelGGL(k_build_append, grid256(ex.nk), dim3(256), 0, c->stream, (const mtb_kmer *)ex.d_k, ex.nk, (const int32_t *)d_t, n_seqs, b->d_rec + b->n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b->n += ex.nk;
+    return MTB_OK;
+}
+
+mtb_status mtb_builder_add_index(mtb_builder *b, mtb_index *ix) {
+    if (!b || !ix) return fail(MTB_ERR_ARG, "NULL argument");
+    if (ix->parent) return fail(MTB_ERR_ARG, "a view cannot be added to a builder: add its parent");
+    mtb_ctx *c = b->ctx;
+    if (ix->ctx->device != c->device) return fail(MTB_ERR_ARG, "the index lives on another device than the builder");
+    if (ix->params.kmer_format != b->params.kmer_format || (ix->params.syncmer != 0) != (b->params.syncmer != 0) ||
+        (b->params.syncmer && ix->params.smer_len != b->params.smer_len))
+        return fail(MTB_ERR_ARG, "the index's kmer_format / syncmer / smer_len differ from the builder's");
+    if (ix->T == 0) return MTB_OK;
+    HIPCHK(hipSetDevice(c->device));
+    STCHK(builder_reserve(b, ix->T));
+    IndexUse use;                                /* a sealed or packed index goes back to {value[], info[]}, as for mtb_index_download, and stays flat (a join's hold) until the d2h below has synchronised the stream */
+    STCHK(use.acquire(ix, false));
+    unsigned long long *d_bad = scal<unsigned long long>(c, SC_JOIN_COUNT);
+    HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
+    mtb_tax_view tv; memset(&tv, 0, sizeof(tv)); tv.canon = b->d_canon; tv.max_taxid = b->tax.max_id;
+    hipLaunchKernelGGL(k_build_from_index, grid256(ix->T), dim3(256), 0, c->stream, (const uint64_t *)ix->d_values, (const uint32_t *)ix->d_info, ix->T, ix->info_mask, tv,
+                       b->d_rec + b->n, d_bad);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad = 0;
+    STCHK(d2h(c, &bad, d_bad, 8));
+    if (bad != ~0ull) {
+        mtb_kmer r;
+        STCHK(d2h(c, &r, b->d_rec + b->n + bad, sizeof(r)));
+        return fail(MTB_ERR_ARG, "taxid " + std::to_string((int32_t)(uint32_t)r.qinfo) + " of the index (entry " + std::to_string(bad) + ") is not in the builder's taxonomy");
+    }
+    b->n += ix->T;
+    return MTB_OK;
+}
+
+mtb_status mtb_builder_finish(mtb_builder *b, mtb_index **out) {
+    if (!b || !out) return fail(MTB_ERR_ARG, "NULL argument");
+    *out = nullptr;
+    const uint64_t n = b->n;
+    if (n == 0) return fail(MTB_ERR_ARG, "the builder holds no records");
+    if (n >= (1ull << 32)) return fail(MTB_ERR_ARG, "2^32 or more records in one finish (" + std::to_string(n) + "): the device sort takes fewer than 2^32; build in parts and merge them with mtb_builder_add_index");
+    mtb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    mtb_index *ix = new mtb_index();
+    /* on every way out but the good one: the half-built index goes, and so do the input-sized sort and reduce buffers */
+    struct Guard { mtb_index *ix; mtb_ctx *c; ~Guard() { if (!ix) return; mtb_index_close(ix); c->last_sorted = nullptr; c->last_sorted_n = 0; std::lock_guard<std::mutex> lk(c->reserve_mu); release_workspace(c); } } guard{ix, c};
+    ix->ctx = c; ix->params = b->params; ix->own = true; ix->info_mask = 0xFFFFFFFFu;
+    ix->tax = b->tax;
+    {   /* the union of the ids added = the new database's taxID_list: the species table comes from it as at index open */
+        const size_t nt = (size_t)b->tax.max_id + 1;
+        uint8_t *d_seen;
+        STCHK(ensure(c, "wseen", nt + 1, &d_seen));
+        HIPCHK(hipMemsetAsync(d_seen, 0, nt + 1, st));
+        hipLaunchKernelGGL(k_build_mark, grid256(n), dim3(256), 0, st, (const mtb_kmer *)b->d_rec, n, d_seen, b->tax.max_id);
+        HIPCHK(hipGetLastError());
+        std::vector<uint8_t> seen(nt);
+        STCHK(d2h(c, seen.data(), d_seen, nt));
+        release(c, "wseen");
+        std::vector<int32_t> ids;
+        for (size_t t = 0; t < nt; t++) if (seen[t]) ids.push_back((int32_t)t);
+        mtbhost::build_tax2species(&ix->tax, ids.data(), ids.size());
+    }
+    STCHK(upload_taxonomy(ix));
+    const int bits = mtb_build_tax_bits(b->tax.max_id);
+    hipEvent_t *ev = b->ev;
+    mtb_kmer *d_a, *d_s;
+    STCHK(ensure(c, "kmersA", n, &d_a));
+    HIPCHK(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(k_build_keys, grid256(n), dim3(256), 0, st, (const mtb_kmer *)b->d_rec, n, (const int32_t *)ix->d_tax2species, b->tax.max_id, bits, d_a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], st));
+    STCHK(dev_sort(c, d_a, n, mtb_build_key_first_bit(bits), &d_s, nullptr, 0));      /* stable: (species, taxid) */
+    hipLaunchKernelGGL(k_build_swap, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, bits, d_a);     /* always into "kmersA": dev_sort's other buffer is "kmersB" */
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[2], st));
+    STCHK(dev_sort(c, d_a, n, /* every bit */ 0, &d_s, nullptr, 0));                 /* stable: (value, species, taxid) */
+    HIPCHK(hipEventRecord(ev[3], st));
+    uint32_t *d_head, *d_pos, *d_list; uint64_t *d_ws;
+    STCHK(ensure(c, "bhead", n, &d_head)); STCHK(ensure(c, "bpos", n + 1, &d_pos));
+    STCHK(ensure(c, "scanws", scan_ws_elems(n + 1), &d_ws));
+    hipLaunchKernelGGL(k_build_heads, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, d_head);
+    scan_launch<uint32_t, uint32_t, false>(st, d_head, n, true, d_pos, (uint32_t *)d_ws);
+    HIPCHK(hipGetLastError());
+    uint32_t n_groups = 0;
+    STCHK(d2h(c, &n_groups, d_pos + n, 4));
+    HIPCHK(hipEventRecord(ev[4], st));
+    const uint64_t G = n_groups;
+    {   hipError_t e = hipMalloc((void **)&ix->d_values, (G + 1) * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&ix->d_info, std::max<uint64_t>(G, 1) * 4);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(MTB_ERR_OOM, "not enough HBM for the built index (" + std::to_string(G) + " entries)"); } }
+    STCHK(ensure(c, "blist", n / (MTB_BUILD_LANE_MAX + 1) + 2, &d_list));
+    uint32_t *d_nlist = scal<uint32_t>(c, SC_JOIN_COUNT);
+    HIPCHK(scal_clear(c, SC_JOIN_COUNT));
+    const mtb_tax_view tv = tax_view(ix);
+    hipLaunchKernelGGL(k_build_reduce, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv, ix->d_values, ix->d_info, d_list, d_nlist);
+    HIPCHK(hipGetLastError());
+    uint32_t n_long = 0;
+    STCHK(d2h(c, &n_long, d_nlist, 4));
+    if (n_long) {
+        hipLaunchKernelGGL(k_build_reduce_long, dim3(std::min<uint32_t>(n_long, 1u << 16)), dim3(64), 0, st, (const mtb_kmer *)d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv,
+                           ix->d_values, ix->d_info, (const uint32_t *)d_list, (const uint32_t *)d_nlist);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(ev[5], st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int k = 0; k < 5; k++) { float ms = 0; if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) (void)hipGetLastError(); b->ms[k] = ms; }
+    { float ms = 0; if (hipEventElapsedTime(&ms, ev[0], ev[5]) != hipSuccess) (void)hipGetLastError(); b->ms[5] = ms; }
+    b->last_n = n; b->last_groups = G; b->last_long = n_long;
+    ix->T = G;
+    /* the sort's and the reduce's buffers are as large as the input: the workspace goes back (as when an index open needs the room) before the directory is built */
+    c->last_sorted = nullptr; c->last_sorted_n = 0;
+    { std::lock_guard<std::mutex> lk(c->reserve_mu); release_workspace(c); }
+    STCHK(build_directory(c, ix));
+    { hipError_t e = hipFree(b->d_rec); (void)e; b->d_rec = nullptr; b->n = 0; b->cap = 0; }      /* empty, reusable */
+    guard.ix = nullptr;
+    *out = ix;
+    return MTB_OK;
+}
+
+mtb_status mtb_builder_last_finish_stats(const mtb_builder *b, mtb_build_stats *out) {
+    if (!b || !out) return fail(MTB_ERR_ARG, "NULL argument");
+    for (int k = 0; k < MTB_BUILD_STAGES; k++) out->ms[k] = b->ms[k];
+    out->n_records = b->last_n; out->n_entries = b->last_groups; out->n_long_groups = b->last_long;
     return MTB_OK;
 }
 

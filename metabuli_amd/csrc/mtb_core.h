@@ -462,6 +462,35 @@ MTB_HD int32_t mtb_lca(const mtb_tax_view *t, int32_t a, int32_t b) {
     return a;
 }
 
+/* ------------------------------------------------------------------ */
+/* Database build (kernels_build.h): per-record arithmetic              */
+/* ------------------------------------------------------------------ */
+/* Kmer::compareTargetKmer (Kmer.h:77-87) orders target entries by (value, speciesId, taxId).  The secondary key of a record is
+ * (species << 32) | taxid; for the radix sort it is squeezed into the 2 * bits top bits of a word (bits = what max_taxid needs), so
+ * that the passes cover only bits that can differ. */
+MTB_HD int mtb_build_tax_bits(int32_t max_taxid) { int b = 1; while (b < 31 && ((int64_t)1 << b) <= (int64_t)max_taxid) b++; return b; }
+MTB_HD uint64_t mtb_build_key(int32_t species, int32_t taxid) { return ((uint64_t)(uint32_t)species << 32) | (uint64_t)(uint32_t)taxid; }
+MTB_HD int32_t mtb_build_key_species(uint64_t key) { return (int32_t)(uint32_t)(key >> 32); }
+MTB_HD int32_t mtb_build_key_taxid(uint64_t key) { return (int32_t)(uint32_t)key; }
+MTB_HD uint64_t mtb_build_sort_key(uint64_t key, int bits) { return (((key >> 32) << bits) | (key & 0xFFFFFFFFull)) << (64 - 2 * bits); }
+MTB_HD uint64_t mtb_build_unsort_key(uint64_t sk, int bits) {
+    const uint64_t k = sk >> (64 - 2 * bits);
+    return ((k >> bits) << 32) | (k & (((uint64_t)1 << bits) - 1ull));
+}
+/* first bit of the key sort's binary passes (they take 8 bits each, up to bit 64) */
+MTB_HD int mtb_build_key_first_bit(int bits) { return (64 - 2 * bits) & ~7; }
+MTB_HD int32_t mtb_build_species(const int32_t *tax2species, int32_t max_taxid, int32_t taxid) { return (taxid >= 0 && taxid <= max_taxid) ? tax2species[taxid] : 0; }
+/* filterKmers<DB_CREATION> (IndexCreator.h:476-615) starts a new entry where (value, speciesId) changes */
+MTB_HD bool mtb_build_is_head(uint64_t prev_value, uint64_t prev_key, uint64_t value, uint64_t key) {
+    return value != prev_value || mtb_build_key_species(key) != mtb_build_key_species(prev_key);
+}
+/* One step of the group's fold, taxonomy->LCA(taxIds of the group): acc = -1 is "nothing yet" (mtb_lca hands the other node back), and a
+ * group of one yields the canonical node, as NcbiTaxonomy::LCA(vector) returns a node and not the raw id.  Partial results combine
+ * with mtb_build_fold_join.  Every id exists (the builder refuses others) and all nodes hang off one root, so LCA is associative and
+ * commutative here: the fold may associate in any order. */
+MTB_HD int32_t mtb_build_fold(const mtb_tax_view *t, int32_t acc, int32_t taxid) { return mtb_lca(t, acc, mtb_tax_canon(t, taxid)); }
+MTB_HD int32_t mtb_build_fold_join(const mtb_tax_view *t, int32_t a, int32_t b) { return mtb_lca(t, a, b); }
+
 /* Match.h:32-44 / Taxonomer.cpp:650-661: score of the `n` codons starting at
  * 2-bit field `first`, walking up (dir=+1) or down (dir=-1) */
 MTB_HD float mtb_codon_score(uint32_t h) { return h == 0 ? 3.0f : 2.0f - 0.5f * (float)h; }
