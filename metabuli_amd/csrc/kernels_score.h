@@ -371,7 +371,7 @@ __device__ __forceinline__ void score_read_par(const REC *src, int32_t n, mtb_sw
                     if (sh && cm) {
                         const int32_t shift = (int32_t)(sh & 0x7Fu);
                         const uint32_t reh = w.m[i].right_end_hamming;
-                        is = mtb_part_score(reh, shift, false); ihd = (mtb_part_ham(reh, shift, false) << 16) | shift; is_root = false;
+                        mtb_link_inc(reh, shift, &is, &ihd); is_root = false;
                     }
                 }
                 ps[k] = wave_inclusive_scan_dpp(is) + carry_s; phd[k] = wave_inclusive_scan_dpp(ihd) + carry_hd;
@@ -393,7 +393,7 @@ __device__ __forceinline__ void score_read_par(const REC *src, int32_t n, mtb_sw
             if (i < n) {
                 const mtb_jump pr = pre[root[k]];
                 const int32_t dhd = phd[k] - pr.ham;
-                fin[k].ptr = root[k] == i ? -1 : root[k]; fin[k].score = ps[k] - pr.score; fin[k].ham = dhd >> 16; fin[k].depth = dhd & 0xFFFF;
+                fin[k].ptr = root[k] == i ? -1 : root[k]; fin[k].score = ps[k] - pr.score; fin[k].ham = mtb_link_ham(dhd); fin[k].depth = mtb_link_depth(dhd);
             }
         }
         score_sync<IDX>();
@@ -412,7 +412,7 @@ __device__ __forceinline__ void score_read_par(const REC *src, int32_t n, mtb_sw
                 if (sh && cm) {
                     const int32_t shift = (int32_t)(sh & 0x7Fu);
                     const uint32_t reh = w.m[i].right_end_hamming;
-                    is = mtb_part_score(reh, shift, false); ihd = (mtb_part_ham(reh, shift, false) << 16) | shift; is_root = false;
+                    mtb_link_inc(reh, shift, &is, &ihd); is_root = false;
                 }
             }
             const float ps = wave_inclusive_scan_dpp(is) + carry_s; const int32_t phd = wave_inclusive_scan_dpp(ihd) + carry_hd;
@@ -427,7 +427,7 @@ __device__ __forceinline__ void score_read_par(const REC *src, int32_t n, mtb_sw
         for (int32_t i = lane; i < n; i += 64) {
             const mtb_jump me = pre[i], pr = pre[me.ptr];
             const int32_t dhd = me.ham - pr.ham;
-            mtb_jump fin; fin.ptr = me.ptr == i ? -1 : me.ptr; fin.score = me.score - pr.score; fin.ham = dhd >> 16; fin.depth = dhd & 0xFFFF;
+            mtb_jump fin; fin.ptr = me.ptr == i ? -1 : me.ptr; fin.score = me.score - pr.score; fin.ham = mtb_link_ham(dhd); fin.depth = mtb_link_depth(dhd);
             w.path[i] = mtb_ph_jump_final(w, i, fin);
         }
         score_sync<IDX>();
@@ -576,23 +576,7 @@ __device__ __forceinline__ void score_read_par(const REC *src, int32_t n, mtb_sw
                     while (mask && !drop) {
                         const int32_t b = a0 + (int32_t)__builtin_ctzll(mask); mask &= mask - 1;
                         const mtb_path c = w.path[w.acc[lo + b]];
-                        if (!((p.end < c.start) || (c.end < p.start))) {
-                            const int32_t ov2 = (p.end < c.end ? p.end : c.end) - (p.start > c.start ? p.start : c.start) + 1;
-                            if (ov2 == p.end - p.start + 1) { drop = true; break; }
-                            if (ov2 < 24) {
-                                if (p.start < c.start) {
-                                    p.end = c.start - 1;
-                                    const int32_t h = p.ham - mtb_part_ham(w.m[pi].right_end_hamming, ov2 / 3, false);
-                                    p.ham = h > 0 ? h : 0;
-                                    p.score = p.score - mtb_part_score(w.m[pi].right_end_hamming, ov2 / 3, false) - (float)(ov2 % 3);
-                                } else {
-                                    p.start = c.end + 1;
-                                    const int32_t h = p.ham - mtb_part_ham(w.m[p.start_idx].right_end_hamming, ov2 / 3, true);
-                                    p.ham = h > 0 ? h : 0;
-                                    p.score = p.score - mtb_part_score(w.m[p.start_idx].right_end_hamming, ov2 / 3, true) - (float)(ov2 % 3);
-                                }
-                            } else drop = true;
-                        }
+                        drop = mtb_path_against(p, c.start, c.end, [&] { return w.m[pi].right_end_hamming; }, [&] { return w.m[p.start_idx].right_end_hamming; });
                     }
                 }
                 if (!drop) {
@@ -639,7 +623,6 @@ __device__ __forceinline__ void score_read_par(const REC *src, int32_t n, mtb_sw
         score_sync<IDX>();
         MTB_PHASE_MARK(11);
         /* sub-species descent: climb the (few) taxa in parallel, walk the chains on lane 0 */
-        bool to_parent = R.score < sp.min_sp_score;          /* R valid on lane 0 only; recomputed below on lane 0 */
         int32_t slow = ntc > MTB_LR_MAXE ? 1 : 0;
         if (!slow && lane < ntc) {
             int32_t lv;
@@ -652,11 +635,7 @@ __device__ __forceinline__ void score_read_par(const REC *src, int32_t n, mtb_sw
         MTB_PHASE_MARK(12);
         if (lane == 0) {
             R.n_taxcnt = (uint16_t)ntc;
-            to_parent = R.score < sp.min_sp_score;
-            int32_t cs = mtb_tax_canon(&tx, species);
-            if (to_parent) R.classification = (species >= 0 && species <= tx.max_taxid) ? tx.sp_parent[species] : 0;
-            else if (slow || cs < 0) R.classification = mtb_lower_rank(&tx, otax, ocnt, ntc, species, read_len, sp.denominator, sp.accession_level);
-            else R.classification = mtb_lr_bfs(lr_lev, lr_anc, ocnt, ntc, cs, read_len, sp.denominator, &tx, sp.accession_level);
+            R.classification = mtb_finish_taxon(&tx, &sp, species, mtb_tax_canon(&tx, species), R.score, slow != 0, lr_lev, lr_anc, otax, ocnt, ntc, read_len);
             R.taxcnt_off = (uint32_t)tc_off;
             for (int32_t k = 0; k < ntc; k++)
                 if (tc_off + k < tc_cap) { tc_tax[tc_off + k] = otax[k]; tc_cnt[tc_off + k] = ocnt[k]; }
@@ -726,9 +705,7 @@ __global__ __launch_bounds__(64, (CAP > MTB_SCORE_LDS ? 2 : MTB_SCORE_MINWAVES))
         }
         const int32_t ql1 = qlen[r], ql2 = qlen2[r];
         const int32_t read_len = ql1 + ql2;
-        mtb_result R;
-        R.classification = 0; R.score = 0.0f; R.query_length = ql1; R.query_length2 = ql2;
-        R.is_classified = 0; R.reserved = 0; R.n_taxcnt = 0; R.taxcnt_off = 0;
+        mtb_result R = mtb_result_blank(ql1, ql2, 0);
         const int32_t nb = mtb_num_buckets(read_len, sp.dna_shift);
         const uint64_t off = tc_off[r], room = tc_off[r + 1] - off;
         if (SLOT) {

@@ -206,8 +206,7 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
             }
         }
         MTB_FAST_MARK(1);       /* species order + keys to LDS (includes the wait for the slot loads) */
-        mtb_result R;
-        R.classification = 0; R.score = 0.0f; R.query_length = ql1; R.query_length2 = ql2; R.is_classified = 0; R.reserved = 0; R.n_taxcnt = 0; R.taxcnt_off = (uint32_t)tc_base;
+        mtb_result R = mtb_result_blank(ql1, ql2, (uint32_t)tc_base);
         if (!slow && n == 0) { if (lane == 0) { cnt_out[r] = (uint32_t)n_live; results[r] = R; } continue; }
         wave_fence();
         /* ---- tail matches into their places.  The further matches of a multi-match metamer sit in the read's tail slots, i.e. at the
@@ -349,7 +348,7 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
                 if (k < nslot) {
                     const int32_t i = lane + 64 * k;
                     float is = 0.0f; int32_t ihd = 0;
-                    if (linked[k]) { is = mtb_part_score(reh[k], shv[k], false); ihd = (mtb_part_ham(reh[k], shv[k], false) << 16) | shv[k]; }
+                    if (linked[k]) mtb_link_inc(reh[k], shv[k], &is, &ihd);
                     ps[k] = wave_inclusive_scan_dpp(is) + carry_s; phd[k] = wave_inclusive_scan_dpp(ihd) + carry_hd;
                     carry_s = rl_f(ps[k], 63); carry_hd = rl_i(phd[k], 63);
                     const uint64_t mr = rmask[k];
@@ -383,13 +382,13 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
                     const uint64_t pr = s_pp[rt]; const FKey rkey = s_key[rt];
                     const uint32_t rreh = (uint32_t)(s_aux[rt] >> 32);
                     const int32_t dhd = phd[k] - (int32_t)(uint32_t)(pr >> 32);
-                    const int32_t depth = 1 + (dhd & 0xFFFF);
+                    const int32_t depth = 1 + mtb_link_depth(dhd);
                     if (depth >= md) {
                         e = true;
                         P.start = (int32_t)fk_pos(rkey);
                         P.end = (int32_t)fk_pos(key[k]) + 23;
                         P.score = mtb_part_score(rreh, 8, false) + (rt == lane + 64 * k ? 0.0f : ps[k] - __uint_as_float((uint32_t)pr));
-                        P.ham = (int32_t)fk_ham(rkey) + (rt == lane + 64 * k ? 0 : (dhd >> 16));
+                        P.ham = (int32_t)fk_ham(rkey) + (rt == lane + 64 * k ? 0 : mtb_link_ham(dhd));
                         P.rehs = rreh | (reh[k] << 16);
                         P.species = spc;
                     }
@@ -435,7 +434,7 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
             bool surv = in;
             if (in && lane != bl && !((P.end < f_st) || (f_en < P.start))) {
                 const int32_t ov = (P.end < f_en ? P.end : f_en) - (P.start > f_st ? P.start : f_st) + 1;
-                if (ov == P.end - P.start + 1 || ov >= 24) surv = false;
+                if (mtb_overlap_drops(ov, P.end - P.start + 1)) surv = false;
             }
             const uint64_t smask = __ballot(surv);
             int32_t rank = 0;
@@ -449,29 +448,16 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
             int32_t acc_st = 0, acc_en = 0, na = 0; float sum = 0.0f;
             for (int32_t q = 0; q < ns; q++) {
                 const int32_t o = (int32_t)__builtin_ctzll(__ballot(surv && rank == q));
-                int32_t cst = rl_i(P.start, o), cen = rl_i(P.end, o), cham = rl_i(P.ham, o);
-                float csc = rl_f(P.score, o);
+                struct { int32_t start, end; float score; int32_t ham; } c;                       /* the candidate, wave-uniform */
+                c.start = rl_i(P.start, o); c.end = rl_i(P.end, o); c.ham = rl_i(P.ham, o); c.score = rl_f(P.score, o);
                 const uint32_t crehs = (uint32_t)rl_i((int32_t)P.rehs, o);
                 bool drop = false;
-                uint64_t ovm = __ballot(lane < na && !((cen < acc_st) || (acc_en < cst)));       /* against the untrimmed candidate: a superset */
+                uint64_t ovm = __ballot(lane < na && !((c.end < acc_st) || (acc_en < c.start)));  /* against the untrimmed candidate: a superset */
                 while (ovm && !drop) {
                     const int32_t a2 = (int32_t)__builtin_ctzll(ovm); ovm &= ovm - 1;
-                    const int32_t ast = rl_i(acc_st, a2), aen = rl_i(acc_en, a2);
-                    if (!((cen < ast) || (aen < cst))) {
-                        const int32_t ov = (cen < aen ? cen : aen) - (cst > ast ? cst : ast) + 1;
-                        if (ov == cen - cst + 1 || ov >= 24) drop = true;
-                        else if (cst < ast) {
-                            cen = ast - 1;
-                            const int32_t h = cham - mtb_part_ham(crehs >> 16, ov / 3, false); cham = h > 0 ? h : 0;
-                            csc = csc - mtb_part_score(crehs >> 16, ov / 3, false) - (float)(ov % 3);
-                        } else {
-                            cst = aen + 1;
-                            const int32_t h = cham - mtb_part_ham(crehs & 0xFFFFu, ov / 3, true); cham = h > 0 ? h : 0;
-                            csc = csc - mtb_part_score(crehs & 0xFFFFu, ov / 3, true) - (float)(ov % 3);
-                        }
-                    }
+                    drop = mtb_path_against(c, rl_i(acc_st, a2), rl_i(acc_en, a2), [&] { return crehs >> 16; }, [&] { return crehs & 0xFFFFu; });
                 }
-                if (!drop) { if (lane == na) { acc_st = cst; acc_en = cen; } na++; sum += csc; }
+                if (!drop) { if (lane == na) { acc_st = c.start; acc_en = c.end; } na++; sum += c.score; }
             }
             float sc = sum / (float)read_len; sc = sc < 1.0f ? sc : 1.0f;
             const int32_t spid = rl_i(P.species, slo);
@@ -480,33 +466,19 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
         MTB_FAST_MARK(5);       /* combination */
         /* ---- species decision (getBestSpeciesMatches second half, chooseBestTaxon early exits) ---- */
         const bool valid = lane < nsp && !(sp_score < sp.min_score);
-        const uint64_t vmask = __ballot(valid);
         const int32_t meaningful = (int32_t)__popcll(__ballot(valid && sp_score > 0.0f));
         if (meaningful == 0) { if (lane == 0) results[r] = R; continue; }
         float best_sp = valid ? sp_score : -1.0f;
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) { const float o2 = __shfl_xor(best_sp, d, 64); best_sp = o2 > best_sp ? o2 : best_sp; }
         const float cut = best_sp * sp.tie_ratio;
-        uint64_t tied = __ballot(valid && sp_score >= cut);
-        const int32_t n_max = (int32_t)__popcll(tied);
-        float tsum = 0.0f; int32_t only = 0, lca = -1, first_spc = 0, cnt_t = 0;
-        for (uint64_t tm = tied; tm; tm &= tm - 1) {
+        mtb_tie tie_sp = mtb_tie_none();
+        for (uint64_t tm = __ballot(valid && sp_score >= cut); tm; tm &= tm - 1) {
             const int32_t s = (int32_t)__builtin_ctzll(tm);
-            const int32_t spc = rl_i(sp_id, s);
-            tsum += rl_f(sp_score, s); only = spc; cnt_t++;
-            if (cnt_t == 1) first_spc = spc;
-            else {
-                if (cnt_t == 2) lca = mtb_tax_exists(&tx, first_spc) ? mtb_tax_canon(&tx, first_spc) : -1;
-                if (mtb_tax_exists(&tx, spc)) lca = lca < 0 ? mtb_tax_canon(&tx, spc) : mtb_lca(&tx, lca, spc);
-            }
+            mtb_tie_add(&tx, &tie_sp, rl_i(sp_id, s), rl_f(sp_score, s));
         }
-        (void)vmask;
-        const float score = n_max > 1 ? tsum / (float)n_max : tsum;
-        R.score = score;
-        if (score == 0.0f || score < sp.min_score) { if (lane == 0) results[r] = R; continue; }
-        if (n_max > 1) { R.is_classified = 1; R.classification = lca < 0 ? 0 : lca; if (lane == 0) results[r] = R; continue; }
-        R.is_classified = 1;
-        const int32_t species = only;
+        if (!mtb_tie_decide(&tie_sp, &sp, &R)) { if (lane == 0) results[r] = R; continue; }
+        const int32_t species = tie_sp.only;
         const bool sp_ok = species >= 0 && species <= tx.max_taxid;
         mtb_tax_node rs = nodes[sp_ok ? species : 0];                              /* needed by the descent: in flight during the filter */
         if (!sp_ok) { rs.canon = -1; rs.depth = 0; rs.parent = -1; rs.flags = 0; }
@@ -531,14 +503,8 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
         for (int k = 0; k < K; k++) {
             if (k < nslot && bq[k] >= 0 && fk_ham(key[k]) == s_hmin[bq[k]]) {
                 const int32_t t = (int32_t)tid[k];
-                int32_t old = atomicCAS(&s_btax[bq[k]], -1, t);              /* the first id of a bucket stays raw */
-                while (old != -1) {
-                    const int32_t merged = old == t ? (tcanon[k] < 0 ? t : tcanon[k]) : mtb_lca(&tx, old, t);      /* LCA(a, a) = canon(a), already here */
-                    if (merged == old) break;
-                    const int32_t seen = atomicCAS(&s_btax[bq[k]], old, merged);
-                    if (seen == old) break;
-                    old = seen;
-                }
+                const int32_t tc = tcanon[k] < 0 ? t : tcanon[k];
+                mtb_bucket_merge(&s_btax[bq[k]], t, [&tx, tc](int32_t a, int32_t b) { return a == b ? tc : mtb_lca(&tx, a, b); });      /* LCA(a, a) = canon(a), already here */
             }
         }
         wave_fence();
@@ -591,10 +557,7 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
         wave_fence();
         if (lane == 0) {
             R.n_taxcnt = (uint16_t)ntc;
-            const int32_t cs = rs.canon;
-            if (R.score < sp.min_sp_score) R.classification = (species >= 0 && species <= tx.max_taxid) ? tx.sp_parent[species] : 0;
-            else if (slow_lr || cs < 0) R.classification = mtb_lower_rank(&tx, s_otax, s_ocnt, ntc, species, read_len, sp.denominator, sp.accession_level);
-            else R.classification = mtb_lr_bfs(s_lev, s_anc, s_ocnt, ntc, cs, read_len, sp.denominator, &tx, sp.accession_level);
+            R.classification = mtb_finish_taxon(&tx, &sp, species, rs.canon, R.score, slow_lr != 0, s_lev, s_anc, s_otax, s_ocnt, ntc, read_len);
             R.taxcnt_off = (uint32_t)(off + tc_base);
             for (int32_t k = 0; k < ntc; k++)
                 if (off + k < tc_cap) { tc_tax[off + k] = s_otax[k]; tc_cnt[off + k] = s_ocnt[k]; }

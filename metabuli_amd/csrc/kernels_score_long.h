@@ -115,11 +115,7 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
         const int32_t ql1 = qlen[r], ql2 = qlen2[r], read_len = ql1 + ql2;
         const int32_t nb = mtb_num_buckets(read_len, sp.dna_shift);
         const uint64_t off = tc_off[r], room = tc_off[r + 1] - off;
-        if (tid == 0) {
-            mtb_result R;
-            R.classification = 0; R.score = 0.0f; R.query_length = ql1; R.query_length2 = ql2; R.is_classified = 0; R.reserved = 0; R.n_taxcnt = 0; R.taxcnt_off = (uint32_t)tc_base;
-            s_R = R;
-        }
+        if (tid == 0) s_R = mtb_result_blank(ql1, ql2, (uint32_t)tc_base);
         if (n < 2) { __syncthreads(); if (tid == 0) results[r] = s_R; continue; }          /* no block of two matches: no path, unclassified */
         if (nb > MAXBKT) { if (tid == 0) todo[r] = 1; continue; }
 
@@ -274,7 +270,7 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
                     }
                     const uint64_t lm = __ballot(linked);
                     float is = 0.0f; int32_t ihd = 0;
-                    if (linked) { is = mtb_part_score(reh, sh, false); ihd = (mtb_part_ham(reh, sh, false) << 16) | sh; }
+                    if (linked) mtb_link_inc(reh, sh, &is, &ihd);
                     const float psum = wave_inclusive_scan_dpp(is); const int32_t phd = wave_inclusive_scan_dpp(ihd);
                     const uint64_t le = ~lm & (lt | (1ull << lane));             /* chain roots at or below this lane; lane 0 is one */
                     const int32_t root = 63 - (int32_t)__builtin_clzll(le);
@@ -283,7 +279,7 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
                     const float r_score = __shfl(p_score, root, 64); const uint32_t r_sreh = (uint32_t)__shfl((int)p_sreh, root, 64);
                     if (linked) {
                         const int32_t dhd = phd - r_phd;
-                        p_start = r_start; p_score = r_score + (psum - r_psum); p_ham = r_ham + (dhd >> 16); p_depth = r_depth + (dhd & 0xFFFF); p_sreh = r_sreh;
+                        p_start = r_start; p_score = r_score + (psum - r_psum); p_ham = r_ham + mtb_link_ham(dhd); p_depth = r_depth + mtb_link_depth(dhd); p_sreh = r_sreh;
                     }
                     if (last >= 1) multi = true;
                     /* a lane whose next group is complete decides its emission now; the last complete group waits for the next
@@ -405,21 +401,7 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
                 mtb_lpath p = s_path[pi];
                 bool drop = lane >= nbt, taken = false;
                 auto against = [&](int32_t cst, int32_t cen) {        /* the reference's loop body for one accepted path */
-                    if (!((p.end < cst) || (cen < p.start))) {
-                        const int32_t ov2 = (p.end < cen ? p.end : cen) - (p.start > cst ? p.start : cst) + 1;
-                        if (ov2 == p.end - p.start + 1) { drop = true; return; }
-                        if (ov2 < 24) {
-                            if (p.start < cst) {
-                                p.end = cst - 1;
-                                const int32_t h = p.ham - mtb_part_ham(p.rehs >> 16, ov2 / 3, false); p.ham = h > 0 ? h : 0;
-                                p.score = p.score - mtb_part_score(p.rehs >> 16, ov2 / 3, false) - (float)(ov2 % 3);
-                            } else {
-                                p.start = cen + 1;
-                                const int32_t h = p.ham - mtb_part_ham(p.rehs & 0xFFFFu, ov2 / 3, true); p.ham = h > 0 ? h : 0;
-                                p.score = p.score - mtb_part_score(p.rehs & 0xFFFFu, ov2 / 3, true) - (float)(ov2 % 3);
-                            }
-                        } else drop = true;
-                    }
+                    drop = mtb_path_against(p, cst, cen, [&] { return p.rehs >> 16; }, [&] { return p.rehs & 0xFFFFu; });
                 };
                 /* the paths accepted before this batch */
                 const int32_t na0 = na;
@@ -461,32 +443,8 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
         /* ---- species decision (thread 0): getBestSpeciesMatches second half, chooseBestTaxon's early exits ---- */
         if (tid == 0) {
             mtb_result R = s_R;
-            float best_sp = 0.0f; int32_t meaningful = 0;
-            for (int32_t j = 0; j < nsp; j++) { const float sc = s_spsc[j]; if (sc < sp.min_score) continue; if (sc > 0.0f) meaningful++; if (sc > best_sp) best_sp = sc; }
-            if (meaningful) {
-                float sum = 0.0f; int32_t n_max = 0, lca = -1, only = 0, first_spc = 0;
-                const float cut = best_sp * sp.tie_ratio;
-                for (int32_t j = 0; j < nsp; j++) {
-                    const float sc = s_spsc[j];
-                    if (sc < sp.min_score) continue;
-                    if (sc >= cut) {
-                        const int32_t spc = s_spid[j];
-                        sum += sc; only = spc; n_max++;
-                        if (n_max == 1) first_spc = spc;
-                        else {
-                            if (n_max == 2) lca = mtb_tax_exists(&tx, first_spc) ? mtb_tax_canon(&tx, first_spc) : -1;
-                            if (mtb_tax_exists(&tx, spc)) lca = lca < 0 ? mtb_tax_canon(&tx, spc) : mtb_lca(&tx, lca, spc);
-                        }
-                    }
-                }
-                const float score = n_max > 1 ? sum / (float)n_max : sum;
-                R.score = score;
-                if (!(score == 0.0f || score < sp.min_score)) {
-                    R.is_classified = 1;
-                    if (n_max > 1) R.classification = lca < 0 ? 0 : lca;
-                    else { s_go = 1; s_species = only; }
-                }
-            }
+            int32_t best = 0, only = 0;
+            if (mtb_select_species(nsp, [&](int32_t j) { return s_spsc[j]; }, [&](int32_t j) { return s_spid[j]; }, &tx, &sp, &R, &best, &only)) { s_go = 1; s_species = only; }
             s_R = R;
         }
         __syncthreads();
@@ -520,23 +478,13 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
                 kn = (kn + 1) & 3;
                 return v;
             };
-            auto merge = [&](int32_t q, int32_t t) {            /* mtb_ph_filter_merge with the memo */
-                int32_t old = atomicCAS(&btax[q], -1, t);       /* first id of the bucket stays raw */
-                while (old != -1) {
-                    const int32_t merged = lca_memo(old, t);
-                    if (merged == old) break;
-                    const int32_t seen = atomicCAS(&btax[q], old, merged);
-                    if (seen == old) break;
-                    old = seen;
-                }
-            };
             for (int32_t c0 = 0; c0 < n; c0 += 2 * MTB_LONG_NT) {
                 const int32_t i0 = c0 + tid, i1 = i0 + MTB_LONG_NT;
                 int32_t s0_ = -1, s1_ = -1, t0 = 0, t1 = 0; uint32_t p0 = 0, p1 = 0, h0 = 0, h1 = 0;
                 if (i0 < n) { s0_ = m[i0].species_id; p0 = mtb_q_pos(m[i0].qinfo); h0 = m[i0].hamming; t0 = m[i0].target_id; }
                 if (i1 < n) { s1_ = m[i1].species_id; p1 = mtb_q_pos(m[i1].qinfo); h1 = m[i1].hamming; t1 = m[i1].target_id; }
-                if (i0 < n && s0_ == species) { const int32_t q = (int32_t)(p0 / (uint32_t)sp.dna_shift); if (q < nb && h0 == hmin[q]) merge(q, t0); }
-                if (i1 < n && s1_ == species) { const int32_t q = (int32_t)(p1 / (uint32_t)sp.dna_shift); if (q < nb && h1 == hmin[q]) merge(q, t1); }
+                if (i0 < n && s0_ == species) { const int32_t q = (int32_t)(p0 / (uint32_t)sp.dna_shift); if (q < nb && h0 == hmin[q]) mtb_bucket_merge(&btax[q], t0, lca_memo); }
+                if (i1 < n && s1_ == species) { const int32_t q = (int32_t)(p1 / (uint32_t)sp.dna_shift); if (q < nb && h1 == hmin[q]) mtb_bucket_merge(&btax[q], t1, lca_memo); }
             }
         }
         __syncthreads();
@@ -583,11 +531,8 @@ __global__ __launch_bounds__(MTB_LONG_NT) void k_score_long(const mtb_match *__r
             mtb_result R = s_R;
             R.n_taxcnt = (uint16_t)ntc;
             const int32_t cs = mtb_tax_canon(&tx, species);
-            if (R.score < sp.min_sp_score) R.classification = (species >= 0 && species <= tx.max_taxid) ? tx.sp_parent[species] : 0;
-            else if (slow || cs < 0) {
-                if (ntc <= MTB_LR_MAXE) R.classification = mtb_lower_rank(&tx, s_otax, s_ocnt, ntc, species, read_len, sp.denominator, sp.accession_level);
-                else R.classification = mtb_lower_rank(&tx, tc_tax + off, tc_cnt + off, ntc, species, read_len, sp.denominator, sp.accession_level);
-            } else R.classification = mtb_lr_bfs(s_lev, s_anc, s_ocnt, ntc, cs, read_len, sp.denominator, &tx, sp.accession_level);
+            if (ntc <= MTB_LR_MAXE) R.classification = mtb_finish_taxon(&tx, &sp, species, cs, R.score, slow != 0, s_lev, s_anc, s_otax, s_ocnt, ntc, read_len);
+            else R.classification = mtb_finish_taxon(&tx, &sp, species, cs, R.score, true, s_lev, s_anc, tc_tax + off, tc_cnt + off, ntc, read_len);      /* a longer list exists in the output arrays only */
             R.taxcnt_off = (uint32_t)(off + tc_base);
             results[r] = R;
         }

@@ -329,9 +329,7 @@ __global__ __launch_bounds__(64, (CAP > 192 ? 2 : 3)) void k_score_many(const mt
         }
         if (hand_on) { if (lane == 0) { rest_list[atomicAdd(n_rest, 1u)] = (uint32_t)r; if (stats) atomicAdd(&stats[why], 1ull); } continue; }
         seen += n_all; kept += n;
-        mtb_result R;
-        R.classification = 0; R.score = 0.0f; R.query_length = ql1; R.query_length2 = ql2;
-        R.is_classified = 0; R.reserved = 0; R.n_taxcnt = 0; R.taxcnt_off = 0;
+        mtb_result R = mtb_result_blank(ql1, ql2, 0);
         if (lane == 0) cnt_out[r] = n_all;
         if (n == 0) { if (lane == 0) results[r] = R; continue; }
         const uint64_t off = tc_off[r], room = tc_off[r + 1] - off;

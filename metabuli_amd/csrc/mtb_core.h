@@ -594,9 +594,35 @@ MTB_HD bool mtb_path_before(const mtb_path &a, const mtb_path &b) {
     return a.start > b.start;
 }
 
+/* One step of combineMatchPaths' greedy loop (Taxonomer.cpp:436-448) with trimMatchPath (:475-485): candidate p against
+ * the accepted path [cst, cen].  An overlap `ov` of the candidate's whole length `len`, or of 24 and more, drops it. */
+MTB_HD bool mtb_overlap_drops(int32_t ov, int32_t len) { return ov == len || ov >= 24; }
+/* Returns true if p is dropped; otherwise a shorter overlap has been trimmed off p's end or start in place.  reh_end() /
+ * reh_start() yield right_end_hamming of the path's end / start match; they are called in the trim branches only. */
+template <typename PATH, typename REH_END, typename REH_START>
+MTB_HD bool mtb_path_against(PATH &p, int32_t cst, int32_t cen, REH_END reh_end, REH_START reh_start) {
+    if ((p.end < cst) || (cen < p.start)) return false;
+    const int32_t ov = (p.end < cen ? p.end : cen) - (p.start > cst ? p.start : cst) + 1;
+    if (mtb_overlap_drops(ov, p.end - p.start + 1)) return true;
+    if (p.start < cst) {
+        p.end = cst - 1;
+        const uint32_t reh = reh_end();
+        const int32_t h = p.ham - mtb_part_ham(reh, ov / 3, false);
+        p.ham = h > 0 ? h : 0;
+        p.score = p.score - mtb_part_score(reh, ov / 3, false) - (float)(ov % 3);
+    } else {
+        p.start = cen + 1;
+        const uint32_t reh = reh_start();
+        const int32_t h = p.ham - mtb_part_ham(reh, ov / 3, true);
+        p.ham = h > 0 ? h : 0;
+        p.score = p.score - mtb_part_score(reh, ov / 3, true) - (float)(ov % 3);
+    }
+    return false;
+}
+
 /* Taxonomer::combineMatchPaths (Taxonomer.cpp:410-468) for the species block
  * m[s..e): stable order of the emitted paths, greedy non-overlap selection
- * with in-place trimming (trimMatchPath, :475-485).  order[] and acc[] are
+ * with in-place trimming (mtb_path_against).  order[] and acc[] are
  * per-match scratch slots.  Returns Sum(score)/read_len; *n_paths = number of
  * emitted paths of the species.                                             */
 MTB_HD float mtb_species_combine(const mtb_match *m, int32_t s, int32_t e, mtb_path *path, const uint8_t *flag,
@@ -618,23 +644,7 @@ MTB_HD float mtb_species_combine(const mtb_match *m, int32_t s, int32_t e, mtb_p
         bool drop = false;
         for (int32_t a = 0; a < na && !drop; a++) {
             const mtb_path &c = path[acc[s + a]];
-            if (!((p.end < c.start) || (c.end < p.start))) {
-                int32_t ov = (p.end < c.end ? p.end : c.end) - (p.start > c.start ? p.start : c.start) + 1;
-                if (ov == p.end - p.start + 1) { drop = true; break; }
-                if (ov < 24) {
-                    if (p.start < c.start) {
-                        p.end = c.start - 1;
-                        int32_t h = p.ham - mtb_part_ham(m[pi].right_end_hamming, ov / 3, false);
-                        p.ham = h > 0 ? h : 0;
-                        p.score = p.score - mtb_part_score(m[pi].right_end_hamming, ov / 3, false) - (float)(ov % 3);
-                    } else {
-                        p.start = c.end + 1;
-                        int32_t h = p.ham - mtb_part_ham(m[p.start_idx].right_end_hamming, ov / 3, true);
-                        p.ham = h > 0 ? h : 0;
-                        p.score = p.score - mtb_part_score(m[p.start_idx].right_end_hamming, ov / 3, true) - (float)(ov % 3);
-                    }
-                } else drop = true;
-            }
+            drop = mtb_path_against(p, c.start, c.end, [&] { return m[pi].right_end_hamming; }, [&] { return m[p.start_idx].right_end_hamming; });
         }
         if (!drop) { acc[s + na++] = pi; score += p.score; }
     }
@@ -739,62 +749,134 @@ MTB_HD int32_t mtb_lower_rank(const mtb_tax_view *tx, const int32_t *tc_tax, con
     return root;
 }
 
-/* Second half of Taxonomer::getBestSpeciesMatches (Taxonomer.cpp:354-407) and
- * the early exits of Taxonomer::chooseBestTaxon (Taxonomer.cpp:130-165) for one
- * read.  sps[s] holds, at the first slot s of every species block,
- * min(combine(),1) or -1 if the species produced no path.  Returns true when
- * a single best species was chosen (then best_s..best_e bound its matches and
- * *species is its id) and the redundancy filter / sub-species descent must run. */
-MTB_HD bool mtb_read_select(const mtb_match *m, int32_t n, const float *sps, const mtb_tax_view *tx,
-                            const mtb_score_params *sp, mtb_result *R, int32_t *best_s_out, int32_t *best_e_out, int32_t *species) {
+/* Sub-species descent on pre-climbed chains (Taxonomer.cpp:252-314):
+ * entry i of the taxCnt map: lev[i] = depth below the species (0 = the species
+ * itself, -1 = not under it), anc[i*K + k] = its ancestor k+1 levels below the
+ * species.  mtb_lr_climb fills them with (parallel) global loads; mtb_lr_bfs
+ * then walks only these arrays.                                             */
+#define MTB_LR_K 4
+#define MTB_LR_MAXE 32
+MTB_HD void mtb_lr_climb(const mtb_tax_view *tx, int32_t tax, int32_t species, int32_t *lev_out, int32_t *anc /* [K] */) {
+    int32_t cs = mtb_tax_canon(tx, species), c = mtb_tax_canon(tx, tax);
+    if (cs < 0 || c < 0) { *lev_out = -1; return; }
+    int32_t dsp = tx->depth[cs];
+    int32_t L = tx->depth[c] - dsp;
+    if (L < 0) { *lev_out = -1; return; }
+    if (L > MTB_LR_K) { *lev_out = MTB_LR_K + 1; return; }      /* too deep: caller falls back */
+    int32_t a = c;
+    for (int32_t k = L - 1; k >= 0; k--) { anc[k] = a; a = tx->parent[a]; }
+    *lev_out = (a == cs) ? L : -1;
+}
+MTB_HD int32_t mtb_lr_bfs(const int32_t *lev, const int32_t *anc, const uint32_t *cnt, int32_t n, int32_t species_canon,
+                          int32_t read_len, int32_t denominator, const mtb_tax_view *tx = 0, int32_t accession_level = 0) {
+    uint32_t thr = (uint32_t)((read_len - 1) / denominator);
+    int32_t root = species_canon;
+    for (int32_t level = 0; level < MTB_LR_K; level++) {
+        /* entries in root's subtree with at least one more level: their child of root is anc[level] */
+        uint32_t max_cnt = thr; int32_t best = -1, n_best = 0; bool any = false;
+        for (int32_t i = 0; i < n; i++) {
+            if (lev[i] <= level) continue;
+            if (level > 0 && anc[i * MTB_LR_K + level - 1] != root) continue;
+            int32_t c = anc[i * MTB_LR_K + level];
+            if (accession_level == 2 && tx && tx->acc_leaf && tx->acc_leaf[c]) continue;      /* Taxonomer.cpp:256-267 */
+            any = true;
+            bool first = true;
+            for (int32_t j = 0; j < i && first; j++)
+                if (lev[j] > level && (level == 0 || anc[j * MTB_LR_K + level - 1] == root) && anc[j * MTB_LR_K + level] == c) first = false;
+            if (!first) continue;
+            uint32_t clade = 0;
+            for (int32_t j = i; j < n; j++)
+                if (lev[j] > level && (level == 0 || anc[j * MTB_LR_K + level - 1] == root) && anc[j * MTB_LR_K + level] == c) clade += cnt[j];
+            if (clade > max_cnt) { best = c; n_best = 1; max_cnt = clade; }
+            else if (clade == max_cnt) { if (n_best == 0) best = c; n_best++; }
+        }
+        if (!any) return root;
+        if (n_best == 1) root = best; else return root;
+    }
+    return root;
+}
+
+/* The blank row of a read: unclassified, score 0, no taxCnt entries. */
+MTB_HD mtb_result mtb_result_blank(int32_t ql1, int32_t ql2, uint32_t taxcnt_off) {
+    mtb_result R;
+    R.classification = 0; R.score = 0.0f; R.query_length = ql1; R.query_length2 = ql2;
+    R.is_classified = 0; R.reserved = 0; R.n_taxcnt = 0; R.taxcnt_off = taxcnt_off;
+    return R;
+}
+
+/* Species within tie_ratio of the best one (Taxonomer.cpp:388-402): their score sum and the LCA of their ids;
+ * LCA(vector) skips unknown ids, and the LCA is only needed once there is a second species. */
+typedef struct { float sum; int32_t n, only, first, lca; } mtb_tie;
+MTB_HD mtb_tie mtb_tie_none(void) { mtb_tie t; t.sum = 0.0f; t.n = 0; t.only = 0; t.first = 0; t.lca = -1; return t; }
+MTB_HD void mtb_tie_add(const mtb_tax_view *tx, mtb_tie *t, int32_t spc, float sc) {
+    t->sum += sc; t->only = spc; t->n++;
+    if (t->n == 1) { t->first = spc; return; }
+    if (t->n == 2) t->lca = mtb_tax_exists(tx, t->first) ? mtb_tax_canon(tx, t->first) : -1;
+    if (mtb_tax_exists(tx, spc)) t->lca = t->lca < 0 ? mtb_tax_canon(tx, spc) : mtb_lca(tx, t->lca, spc);
+}
+/* The early exits of Taxonomer::chooseBestTaxon (Taxonomer.cpp:149-165) on the tied species: sets R's score and, for
+ * several species, their LCA.  Returns true when a single species was chosen (t->only) and the redundancy filter /
+ * sub-species descent must run. */
+MTB_HD bool mtb_tie_decide(const mtb_tie *t, const mtb_score_params *sp, mtb_result *R) {
+    const float score = t->n > 1 ? t->sum / (float)t->n : t->sum;
+    R->score = score;
+    if (score == 0.0f || score < sp->min_score) return false;    /* :149-156 */
+    R->is_classified = 1;
+    if (t->n > 1) { R->classification = t->lca < 0 ? 0 : t->lca; return false; }   /* :159-165 */
+    return true;
+}
+/* Second half of Taxonomer::getBestSpeciesMatches (Taxonomer.cpp:354-407) and the early exits above over n_species
+ * candidates in match order: score_of(s) = min(combine(), 1), or -1 if s produced no path (or is no species at all);
+ * id_of(s) = its species id.  Returns true when a single best species was chosen: *best is its index, *species its id. */
+template <typename SCORE, typename ID>
+MTB_HD bool mtb_select_species(int32_t n_species, SCORE score_of, ID id_of, const mtb_tax_view *tx, const mtb_score_params *sp,
+                               mtb_result *R, int32_t *best, int32_t *species) {
     R->classification = 0; R->score = 0.0f; R->is_classified = 0; R->n_taxcnt = 0;
-    float best_sp = 0.0f; int32_t best_s = 0, best_e = 0; int32_t meaningful = 0;
-    int32_t i = 0;
-    while (i < n) {
-        int32_t s = i; int32_t spc = m[i].species_id;
-        while (i < n && m[i].species_id == spc) i++;
-        float sc = sps[s];
+    float best_sp = 0.0f; int32_t meaningful = 0;
+    for (int32_t s = 0; s < n_species; s++) {
+        const float sc = score_of(s);
         if (sc == -1.0f) continue;                 /* no path for this species          */
         if (sc < sp->min_score) continue;          /* Taxonomer.cpp:357-359             */
         if (sc > 0.0f) meaningful++;
-        if (sc > best_sp) { best_sp = sc; best_s = s; best_e = i; }
+        if (sc > best_sp) { best_sp = sc; *best = s; }
     }
     if (meaningful == 0) return false;             /* score 0, unclassified (:372-375)  */
-    /* ties within tie_ratio (:388-402); LCA(vector) skips unknown ids */
-    float sum = 0.0f; int32_t n_max = 0; int32_t lca = -1; int32_t only = 0, first_spc = 0;
-    float cut = best_sp * sp->tie_ratio;
-    i = 0;
-    while (i < n) {
-        int32_t s = i; int32_t spc = m[i].species_id;
-        while (i < n && m[i].species_id == spc) i++;
-        float sc = sps[s];
+    mtb_tie t = mtb_tie_none();
+    const float cut = best_sp * sp->tie_ratio;
+    for (int32_t s = 0; s < n_species; s++) {
+        const float sc = score_of(s);
         if (sc == -1.0f || sc < sp->min_score) continue;
-        if (sc >= cut) {
-            sum += sc; only = spc; n_max++;
-            if (n_max == 1) first_spc = spc;       /* the LCA is only needed for ties */
-            else {
-                if (n_max == 2) lca = mtb_tax_exists(tx, first_spc) ? mtb_tax_canon(tx, first_spc) : -1;
-                if (mtb_tax_exists(tx, spc)) lca = lca < 0 ? mtb_tax_canon(tx, spc) : mtb_lca(tx, lca, spc);
-            }
-        }
+        if (sc >= cut) mtb_tie_add(tx, &t, id_of(s), sc);
     }
-    float score = n_max > 1 ? sum / (float)n_max : sum;
-    R->score = score;
-    if (score == 0.0f || score < sp->min_score) return false;    /* :149-156 */
-    if (n_max > 1) { R->is_classified = 1; R->classification = lca < 0 ? 0 : lca; return false; }   /* :159-165 */
-    *best_s_out = best_s; *best_e_out = best_e; *species = only;
-    R->is_classified = 1;
+    *species = t.only;
+    return mtb_tie_decide(&t, sp, R);
+}
+/* The same for one read's sorted matches: sps[s] holds the score at the first slot s of every species block.  On
+ * true, best_s..best_e bound the chosen species' matches. */
+MTB_HD bool mtb_read_select(const mtb_match *m, int32_t n, const float *sps, const mtb_tax_view *tx,
+                            const mtb_score_params *sp, mtb_result *R, int32_t *best_s_out, int32_t *best_e_out, int32_t *species) {
+    int32_t bs = 0;
+    const bool go = mtb_select_species(n, [&](int32_t i) { return (i == 0 || m[i].species_id != m[i - 1].species_id) ? sps[i] : -1.0f; },
+                                       [&](int32_t i) { return m[i].species_id; }, tx, sp, R, &bs, species);
+    if (!go) return false;
+    int32_t be = bs;
+    while (be < n && m[be].species_id == m[bs].species_id) be++;
+    *best_s_out = bs; *best_e_out = be;
     return true;
 }
-/* after the redundancy filter: Taxonomer.cpp:178-198 */
+/* After the redundancy filter (Taxonomer.cpp:178-198): a species scoring below min_sp_score yields its parent; otherwise
+ * the descent below the species over the taxCnt list otax/ocnt[ntc], on the pre-climbed chains lev/anc unless they do not
+ * suffice (`slow`: more than MTB_LR_MAXE entries or one deeper than MTB_LR_K; cs = canonical id of the species, < 0 if unknown). */
+MTB_HD int32_t mtb_finish_taxon(const mtb_tax_view *tx, const mtb_score_params *sp, int32_t species, int32_t cs, float score, bool slow,
+                                const int32_t *lev, const int32_t *anc, const int32_t *otax, const uint32_t *ocnt, int32_t ntc, int32_t read_len) {
+    if (score < sp->min_sp_score) return (species >= 0 && species <= tx->max_taxid) ? tx->sp_parent[species] : 0;
+    if (slow || cs < 0) return mtb_lower_rank(tx, otax, ocnt, ntc, species, read_len, sp->denominator, sp->accession_level);
+    return mtb_lr_bfs(lev, anc, ocnt, ntc, cs, read_len, sp->denominator, tx, sp->accession_level);
+}
 MTB_HD void mtb_read_finish(const mtb_tax_view *tx, const mtb_score_params *sp, int32_t species, int32_t read_len,
                             const int32_t *out_tax, const uint32_t *out_cnt, int32_t ntc, mtb_result *R) {
     R->n_taxcnt = (uint16_t)ntc;
-    if (R->score < sp->min_sp_score) {
-        R->classification = (species >= 0 && species <= tx->max_taxid) ? tx->sp_parent[species] : 0;
-        return;
-    }
-    R->classification = mtb_lower_rank(tx, out_tax, out_cnt, ntc, species, read_len, sp->denominator, sp->accession_level);
+    R->classification = mtb_finish_taxon(tx, sp, species, -1, R->score, true, 0, 0, out_tax, out_cnt, ntc, read_len);
 }
 MTB_HD void mtb_read_decide(const mtb_match *m, int32_t n, const float *sps, const mtb_tax_view *tx,
                             const mtb_score_params *sp, int32_t read_len, int32_t *b_tax, uint8_t *b_ham,

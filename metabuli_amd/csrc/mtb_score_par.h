@@ -231,50 +231,8 @@ MTB_HD bool mtb_ph_emit(const mtb_sws<IDX> &w, int32_t i, const mtb_score_params
     int32_t md = (f & MTB_F_EUK) ? sp->min_cons_cnt_euk : sp->min_cons_cnt;
     return (f & MTB_F_MULTI) && !(f & MTB_F_CONN) && w.path[i].depth >= md;
 }
-/* ---- combine (Taxonomer.cpp:410-468) on the emitted list el[lo..hi) ---- */
-template <typename IDX>
-MTB_HD float mtb_ph_combine(const mtb_sws<IDX> &w, IDX *el, int32_t lo, int32_t hi, int32_t read_len) {
-    const mtb_match *m = w.m; mtb_path *path = w.path; IDX *acc = w.acc;
-    /* stable insertion sort: score desc, hamming asc, start desc */
-    for (int32_t a = lo + 1; a < hi; a++) {
-        IDX x = el[a];
-        mtb_path px = path[x];
-        int32_t j = a;
-        while (j > lo && mtb_path_before(px, path[el[j - 1]])) { el[j] = el[j - 1]; j--; }
-        el[j] = x;
-    }
-    float score = 0.0f;
-    int32_t na = 0;
-    for (int32_t k = lo; k < hi; k++) {
-        int32_t pi = el[k];
-        mtb_path p = path[pi];
-        bool drop = false;
-        for (int32_t a = 0; a < na && !drop; a++) {
-            mtb_path c = path[acc[lo + a]];
-            if (!((p.end < c.start) || (c.end < p.start))) {
-                int32_t ov = (p.end < c.end ? p.end : c.end) - (p.start > c.start ? p.start : c.start) + 1;
-                if (ov == p.end - p.start + 1) { drop = true; break; }
-                if (ov < 24) {
-                    if (p.start < c.start) {
-                        p.end = c.start - 1;
-                        int32_t h = p.ham - mtb_part_ham(m[pi].right_end_hamming, ov / 3, false);
-                        p.ham = h > 0 ? h : 0;
-                        p.score = p.score - mtb_part_score(m[pi].right_end_hamming, ov / 3, false) - (float)(ov % 3);
-                    } else {
-                        p.start = c.end + 1;
-                        int32_t h = p.ham - mtb_part_ham(m[p.start_idx].right_end_hamming, ov / 3, true);
-                        p.ham = h > 0 ? h : 0;
-                        p.score = p.score - mtb_part_score(m[p.start_idx].right_end_hamming, ov / 3, true) - (float)(ov % 3);
-                    }
-                } else drop = true;
-            }
-        }
-        if (!drop) { path[pi] = p; acc[lo + na++] = (IDX)pi; score += p.score; }
-    }
-    return score / (float)read_len;
-}
-/* ---- combine in parallel pieces ------------------------------------------------------------------------
- * The insertion sort + greedy pass above is serial per species.  The same result comes from
+/* ---- combine (Taxonomer.cpp:410-468) in parallel pieces -------------------------------------------------
+ * The insertion sort + greedy pass of mtb_species_combine is serial per species.  The same result comes from
  *   comb_lo     emitted entry e -> start `lo` of its species' range in the emitted list (binary search in sp_start)
  *   comb_rank   position of e in the stable (score desc, hamming asc, start desc) order of its species:
  *               lo + #{f in [lo,hi): f strictly before e, or equivalent with f < e}  (== stable insertion sort)
@@ -335,7 +293,7 @@ MTB_HD bool mtb_ph_comb_predrop(const mtb_sws<IDX> &w, const IDX *sorted, int32_
     const mtb_path c = w.path[sorted[lo]], p = w.path[sorted[k]];
     if ((p.end < c.start) || (c.end < p.start)) return false;
     int32_t ov = (p.end < c.end ? p.end : c.end) - (p.start > c.start ? p.start : c.start) + 1;
-    return ov == p.end - p.start + 1 || ov >= 24;
+    return mtb_overlap_drops(ov, p.end - p.start + 1);
 }
 template <typename IDX>
 MTB_HD float mtb_ph_comb_greedy(const mtb_sws<IDX> &w, const IDX *sorted, const uint8_t *predrop, int32_t lo, int32_t hi, int32_t read_len) {
@@ -349,23 +307,7 @@ MTB_HD float mtb_ph_comb_greedy(const mtb_sws<IDX> &w, const IDX *sorted, const 
         bool drop = false;
         for (int32_t a = 0; a < na && !drop; a++) {
             mtb_path c = path[acc[lo + a]];
-            if (!((p.end < c.start) || (c.end < p.start))) {
-                int32_t ov = (p.end < c.end ? p.end : c.end) - (p.start > c.start ? p.start : c.start) + 1;
-                if (ov == p.end - p.start + 1) { drop = true; break; }
-                if (ov < 24) {
-                    if (p.start < c.start) {
-                        p.end = c.start - 1;
-                        int32_t h = p.ham - mtb_part_ham(m[pi].right_end_hamming, ov / 3, false);
-                        p.ham = h > 0 ? h : 0;
-                        p.score = p.score - mtb_part_score(m[pi].right_end_hamming, ov / 3, false) - (float)(ov % 3);
-                    } else {
-                        p.start = c.end + 1;
-                        int32_t h = p.ham - mtb_part_ham(m[p.start_idx].right_end_hamming, ov / 3, true);
-                        p.ham = h > 0 ? h : 0;
-                        p.score = p.score - mtb_part_score(m[p.start_idx].right_end_hamming, ov / 3, true) - (float)(ov % 3);
-                    }
-                } else drop = true;
-            }
+            drop = mtb_path_against(p, c.start, c.end, [&] { return m[pi].right_end_hamming; }, [&] { return m[p.start_idx].right_end_hamming; });
         }
         if (!drop) { path[pi] = p; acc[lo + na++] = (IDX)pi; score += p.score; }
     }
@@ -376,39 +318,11 @@ MTB_HD float mtb_ph_comb_greedy(const mtb_sws<IDX> &w, const IDX *sorted, const 
 template <typename IDX>
 MTB_HD bool mtb_ph_select(const mtb_sws<IDX> &w, const float *sps, int32_t n_species, const mtb_tax_view *tx,
                           const mtb_score_params *sp, mtb_result *R, int32_t *best_s_out, int32_t *best_e_out, int32_t *species) {
-    R->classification = 0; R->score = 0.0f; R->is_classified = 0; R->n_taxcnt = 0;
-    float best_sp = 0.0f; int32_t best = -1; int32_t meaningful = 0;
-    for (int32_t s = 0; s < n_species; s++) {
-        float sc = sps[s];
-        if (sc == -1.0f) continue;
-        if (sc < sp->min_score) continue;
-        if (sc > 0.0f) meaningful++;
-        if (sc > best_sp) { best_sp = sc; best = s; }
-    }
-    if (meaningful == 0) return false;
-    float sum = 0.0f; int32_t n_max = 0; int32_t lca = -1; int32_t only = 0, first_spc = 0;
-    float cut = best_sp * sp->tie_ratio;
-    for (int32_t s = 0; s < n_species; s++) {
-        float sc = sps[s];
-        if (sc == -1.0f || sc < sp->min_score) continue;
-        if (sc >= cut) {
-            int32_t spc = w.m[w.sp_start[s]].species_id;
-            sum += sc; only = spc; n_max++;
-            if (n_max == 1) first_spc = spc;
-            else {
-                if (n_max == 2) lca = mtb_tax_exists(tx, first_spc) ? mtb_tax_canon(tx, first_spc) : -1;
-                if (mtb_tax_exists(tx, spc)) lca = lca < 0 ? mtb_tax_canon(tx, spc) : mtb_lca(tx, lca, spc);
-            }
-        }
-    }
-    float score = n_max > 1 ? sum / (float)n_max : sum;
-    R->score = score;
-    if (score == 0.0f || score < sp->min_score) return false;
-    if (n_max > 1) { R->is_classified = 1; R->classification = lca < 0 ? 0 : lca; return false; }
+    int32_t best = -1;
+    if (!mtb_select_species(n_species, [&](int32_t s) { return sps[s]; }, [&](int32_t s) { return w.m[w.sp_start[s]].species_id; },
+                            tx, sp, R, &best, species)) return false;
     *best_s_out = w.sp_start[best];
     *best_e_out = (best + 1 < n_species) ? (int32_t)w.sp_start[best + 1] : w.n;
-    *species = only;
-    R->is_classified = 1;
     return true;
 }
 
@@ -431,66 +345,23 @@ MTB_HD void mtb_ph_filter_min(const mtb_match *m, int32_t i, int32_t dna_shift, 
     int32_t q = (int32_t)(mtb_q_pos(m[i].qinfo) / (uint32_t)dna_shift);
     if (q < nb) MTB_AMIN_U32(&hmin[q], (uint32_t)m[i].hamming);
 }
-MTB_HD void mtb_ph_filter_merge(const mtb_match *m, int32_t i, int32_t dna_shift, int32_t nb, const uint32_t *hmin,
-                                int32_t *btax, const mtb_tax_view *tx) {
-    int32_t q = (int32_t)(mtb_q_pos(m[i].qinfo) / (uint32_t)dna_shift);
-    if (q >= nb || (uint32_t)m[i].hamming != hmin[q]) return;
-    int32_t tid = m[i].target_id;
-    int32_t old = MTB_ACAS_I32(&btax[q], -1, tid);         /* first id of the bucket stays raw */
+/* one minimum-hamming target id into its bucket; lca(a, b) = LCA of two ids, however the caller obtains it */
+template <typename LCA>
+MTB_HD void mtb_bucket_merge(int32_t *bucket, int32_t tid, LCA lca) {
+    int32_t old = MTB_ACAS_I32(bucket, -1, tid);           /* first id of the bucket stays raw */
     while (old != -1) {
-        int32_t merged = mtb_lca(tx, old, tid);
+        int32_t merged = lca(old, tid);
         if (merged == old) break;
-        int32_t seen = MTB_ACAS_I32(&btax[q], old, merged);
+        int32_t seen = MTB_ACAS_I32(bucket, old, merged);
         if (seen == old) break;
         old = seen;
     }
 }
-
-/* ---- sub-species descent on pre-climbed chains (Taxonomer.cpp:252-314) ----
- * entry i of the taxCnt map: lev[i] = depth below the species (0 = the species
- * itself, -1 = not under it), anc[i*K + k] = its ancestor k+1 levels below the
- * species.  mtb_lr_climb fills them with (parallel) global loads; mtb_lr_bfs
- * then walks only these arrays.                                             */
-#define MTB_LR_K 4
-#define MTB_LR_MAXE 32
-MTB_HD void mtb_lr_climb(const mtb_tax_view *tx, int32_t tax, int32_t species, int32_t *lev_out, int32_t *anc /* [K] */) {
-    int32_t cs = mtb_tax_canon(tx, species), c = mtb_tax_canon(tx, tax);
-    if (cs < 0 || c < 0) { *lev_out = -1; return; }
-    int32_t dsp = tx->depth[cs];
-    int32_t L = tx->depth[c] - dsp;
-    if (L < 0) { *lev_out = -1; return; }
-    if (L > MTB_LR_K) { *lev_out = MTB_LR_K + 1; return; }      /* too deep: caller falls back */
-    int32_t a = c;
-    for (int32_t k = L - 1; k >= 0; k--) { anc[k] = a; a = tx->parent[a]; }
-    *lev_out = (a == cs) ? L : -1;
-}
-MTB_HD int32_t mtb_lr_bfs(const int32_t *lev, const int32_t *anc, const uint32_t *cnt, int32_t n, int32_t species_canon,
-                          int32_t read_len, int32_t denominator, const mtb_tax_view *tx = 0, int32_t accession_level = 0) {
-    uint32_t thr = (uint32_t)((read_len - 1) / denominator);
-    int32_t root = species_canon;
-    for (int32_t level = 0; level < MTB_LR_K; level++) {
-        /* entries in root's subtree with at least one more level: their child of root is anc[level] */
-        uint32_t max_cnt = thr; int32_t best = -1, n_best = 0; bool any = false;
-        for (int32_t i = 0; i < n; i++) {
-            if (lev[i] <= level) continue;
-            if (level > 0 && anc[i * MTB_LR_K + level - 1] != root) continue;
-            int32_t c = anc[i * MTB_LR_K + level];
-            if (accession_level == 2 && tx && tx->acc_leaf && tx->acc_leaf[c]) continue;      /* Taxonomer.cpp:256-267 */
-            any = true;
-            bool first = true;
-            for (int32_t j = 0; j < i && first; j++)
-                if (lev[j] > level && (level == 0 || anc[j * MTB_LR_K + level - 1] == root) && anc[j * MTB_LR_K + level] == c) first = false;
-            if (!first) continue;
-            uint32_t clade = 0;
-            for (int32_t j = i; j < n; j++)
-                if (lev[j] > level && (level == 0 || anc[j * MTB_LR_K + level - 1] == root) && anc[j * MTB_LR_K + level] == c) clade += cnt[j];
-            if (clade > max_cnt) { best = c; n_best = 1; max_cnt = clade; }
-            else if (clade == max_cnt) { if (n_best == 0) best = c; n_best++; }
-        }
-        if (!any) return root;
-        if (n_best == 1) root = best; else return root;
-    }
-    return root;
+MTB_HD void mtb_ph_filter_merge(const mtb_match *m, int32_t i, int32_t dna_shift, int32_t nb, const uint32_t *hmin,
+                                int32_t *btax, const mtb_tax_view *tx) {
+    int32_t q = (int32_t)(mtb_q_pos(m[i].qinfo) / (uint32_t)dna_shift);
+    if (q >= nb || (uint32_t)m[i].hamming != hmin[q]) return;
+    mtb_bucket_merge(&btax[q], m[i].target_id, [&](int32_t a, int32_t b) { return mtb_lca(tx, a, b); });
 }
 
 /* ---- chain DP by pointer doubling -----------------------------------------
@@ -502,6 +373,13 @@ MTB_HD int32_t mtb_lr_bfs(const int32_t *lev, const int32_t *anc, const uint32_t
  * give bit-identical paths.  jump[] lives in the storage of path[] (16 B <= 24 B
  * per match); the final paths are rebuilt from the roots' matches.          */
 typedef struct { int32_t ptr; float score; int32_t ham; int32_t depth; } mtb_jump;
+/* increment of one link for the prefix-sum forms of the DP: the score, and hamming / depth packed into one word
+ * (hamming << 16 | codon shift) so that one integer scan sums both; differences of sums unpack with the two below */
+MTB_HD void mtb_link_inc(uint32_t reh, int32_t shift, float *is, int32_t *ihd) {
+    *is = mtb_part_score(reh, shift, false); *ihd = (mtb_part_ham(reh, shift, false) << 16) | shift;
+}
+MTB_HD int32_t mtb_link_ham(int32_t dhd) { return dhd >> 16; }
+MTB_HD int32_t mtb_link_depth(int32_t dhd) { return dhd & 0xFFFF; }
 
 /* true if match i allows the chain formulation */
 template <typename IDX>

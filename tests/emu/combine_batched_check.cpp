@@ -12,7 +12,8 @@
 #include <vector>
 #include "../../metabuli_amd/csrc/mtb_core.h"
 struct P { int32_t start, end; float score; int32_t ham; uint32_t reh_start, reh_end; };
-static bool against(P &p, int32_t cst, int32_t cen) {          // returns true if the candidate is dropped
+// this file's own statement of the step: returns true if the candidate is dropped
+static bool against_local(P &p, int32_t cst, int32_t cen) {
     if (!((p.end < cst) || (cen < p.start))) {
         const int32_t ov = (p.end < cen ? p.end : cen) - (p.start > cst ? p.start : cst) + 1;
         if (ov == p.end - p.start + 1) return true;
@@ -29,6 +30,17 @@ static bool against(P &p, int32_t cst, int32_t cen) {          // returns true i
         } else return true;
     }
     return false;
+}
+// every call also runs the library's mtb_path_against on a copy: same verdict, same trimmed bytes; the run must see all five outcomes
+static long n_outcome[5];                                       // no overlap, whole length, >= 24, end trim, start trim
+static bool against(P &p, int32_t cst, int32_t cen) {
+    P q = p; const P p0 = p;
+    const bool drop = against_local(p, cst, cen);
+    const bool drop_lib = mtb_path_against(q, cst, cen, [&] { return q.reh_end; }, [&] { return q.reh_start; });
+    if (drop != drop_lib || memcmp(&p, &q, sizeof(P))) { printf("MISMATCH mtb_path_against: [%d, %d] against [%d, %d]\n", p0.start, p0.end, cst, cen); exit(1); }
+    const bool disjoint = p0.end < cst || cen < p0.start;
+    n_outcome[disjoint ? 0 : drop ? (p0.start >= cst && p0.end <= cen ? 1 : 2) : (p.end != p0.end ? 3 : 4)]++;
+    return drop;
 }
 static float serial(std::vector<P> c, std::vector<P> *acc) {
     float score = 0.0f;
@@ -75,6 +87,7 @@ int main(int argc, char **argv) {
         for (size_t k = 0; k < a1.size(); k++)
             if (memcmp(&a1[k], &a2[k], sizeof(P)) || memcmp(&a1[k], &a3[k], sizeof(P))) { printf("MISMATCH round %d path %zu\n", it, k); return 1; }
     }
+    for (int k = 0; k < 5; k++) if (!n_outcome[k]) { printf("MISSED outcome %d of the greedy step\n", k); return 1; }
     printf("OK %d\n", rounds);
     return 0;
 }

@@ -106,7 +106,7 @@ size_t emu_score(const uint8_t *acc_leaf, const int32_t *canon, const int32_t *p
                  mtb_result *res, int32_t *tc_tax, uint32_t *tc_cnt, size_t cap) {
     mtb_tax_view tx{acc_leaf, canon, parent, depth, under_euk, sp_parent, max_taxid};
     mtb_score_params sp; mtb_make_score_params(p, &sp);
-    for (size_t r = 0; r < n_reads; r++) { res[r] = mtb_result{0, 0.f, qlen[r], qlen2 ? qlen2[r] : 0, 0, 0, 0, 0}; }
+    for (size_t r = 0; r < n_reads; r++) res[r] = mtb_result_blank(qlen[r], qlen2 ? qlen2[r] : 0, 0);
     size_t w = 0, idx = 0;
     while (idx < nM) {
         uint32_t seq = mtb_q_seq(ml[idx].qinfo);
@@ -159,7 +159,7 @@ size_t emu_score_par(const uint8_t *acc_leaf, const int32_t *canon, const int32_
     size_t n_chain_reads = 0;
     mtb_tax_view tx{acc_leaf, canon, parent, depth, under_euk, sp_parent, max_taxid};
     mtb_score_params sp; mtb_make_score_params(p, &sp);
-    for (size_t r = 0; r < n_reads; r++) { res[r] = mtb_result{0, 0.f, qlen[r], qlen2 ? qlen2[r] : 0, 0, 0, 0, 0}; }
+    for (size_t r = 0; r < n_reads; r++) res[r] = mtb_result_blank(qlen[r], qlen2 ? qlen2[r] : 0, 0);
     size_t wout = 0, idx = 0;
     typedef uint16_t IDX;
     while (idx < nM) {
@@ -270,15 +270,10 @@ size_t emu_score_par(const uint8_t *acc_leaf, const int32_t *canon, const int32_
             for (int32_t q = 0; q < nb; q++) bham[(size_t)q] = hmin[(size_t)q] == 255 ? 255 : 0;
             int32_t ntc = mtb_taxcnt_gather(btax.data(), bham.data(), nb, otax.data(), ocnt.data(), nb);
             R.n_taxcnt = (uint16_t)ntc;
-            if (R.score < sp.min_sp_score) R.classification = (species >= 0 && species <= max_taxid) ? sp_parent[species] : 0;
-            else {
-                bool slow = ntc > MTB_LR_MAXE;
-                std::vector<int32_t> lev((size_t)std::max(ntc, 1)), anc((size_t)std::max(ntc, 1) * MTB_LR_K);
-                if (!slow) for (int32_t i = 0; i < ntc; i++) { mtb_lr_climb(&tx, otax[(size_t)i], species, &lev[(size_t)i], &anc[(size_t)i * MTB_LR_K]); if (lev[(size_t)i] > MTB_LR_K) slow = true; }
-                int32_t cs = mtb_tax_canon(&tx, species);
-                if (slow || cs < 0) R.classification = mtb_lower_rank(&tx, otax.data(), ocnt.data(), ntc, species, read_len, sp.denominator, sp.accession_level);
-                else R.classification = mtb_lr_bfs(lev.data(), anc.data(), ocnt.data(), ntc, cs, read_len, sp.denominator, &tx, sp.accession_level);
-            }
+            bool slow = ntc > MTB_LR_MAXE;
+            std::vector<int32_t> lev((size_t)std::max(ntc, 1)), anc((size_t)std::max(ntc, 1) * MTB_LR_K);
+            if (!slow) for (int32_t i = 0; i < ntc; i++) { mtb_lr_climb(&tx, otax[(size_t)i], species, &lev[(size_t)i], &anc[(size_t)i * MTB_LR_K]); if (lev[(size_t)i] > MTB_LR_K) slow = true; }
+            R.classification = mtb_finish_taxon(&tx, &sp, species, mtb_tax_canon(&tx, species), R.score, slow, lev.data(), anc.data(), otax.data(), ocnt.data(), ntc, read_len);
             for (int32_t k = 0; k < ntc; k++) { if (wout < cap) { tc_tax[wout] = otax[(size_t)k]; tc_cnt[wout] = ocnt[(size_t)k]; } wout++; }
         }
         res[r] = R;
