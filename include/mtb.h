@@ -471,9 +471,13 @@ mtb_status mtb_extract_targets(mtb_ctx *, const mtb_params *, const char *genome
  * s = taxId2speciesId[taxid] (the table mtb_index_open builds, here from the union of the ids added, which is the new database's
  * taxID_list), one entry per distinct (value, s) whose info is the LCA of the group's taxids (the canonical node: a group of one
  * gives the merged.dmp target of its id), in (value, s) order.
- * Gene prediction is NOT part of this: mtb_builder_add_sequences extracts every sequence in all six frames (long-read geometry),
- * as the toy and benchmark databases are built, not the reference's Prodigal-guided extraction; a caller with CDS-restricted
- * metamers passes them to mtb_builder_add_records.
+ * Two extraction routes.  mtb_builder_add_sequences extracts every sequence in all six frames (long-read geometry), as the toy and
+ * benchmark databases are built.  mtb_builder_add_blocks scans sequence BLOCKS, each in one frame on one strand, which is how the
+ * reference builds (IndexCreator feeds KmerExtractor::extractTargetKmers blocks, KmerExtractor.cpp:407-426): with blocks made from
+ * a CDS annotation (metabuli_amd/csrc/host/cds_info.h, `mtb_build --cds-info`) the records are those of the reference's
+ * `build --cds-info LIST --mask 0`.  Gene PREDICTION is still not part of this: Prodigal (the reference's route for genomes without
+ * an annotation) and tantan masking are not implemented; a caller with metamers from elsewhere passes them to
+ * mtb_builder_add_records.
  * `params` fixes kmer_format, syncmer and smer_len of everything added.  Every taxid added must exist in the taxonomy (after
  * merged.dmp aliasing): otherwise the call returns MTB_ERR_ARG, mtb_last_error() names the first offending id and the builder
  * holds what it held before.  All pointers are host memory.
@@ -491,6 +495,23 @@ mtb_status mtb_builder_create(mtb_ctx *, const char *taxonomy_dir, const mtb_par
 mtb_status mtb_builder_add_sequences(mtb_builder *, const char *bases, const uint64_t *offs,
                                      const int32_t *taxids, uint64_t n_seqs);
 mtb_status mtb_builder_add_records(mtb_builder *, const uint64_t *values, const int32_t *taxids, uint64_t n);
+/* A block of a sequence, scanned in ONE frame on ONE strand (KmerScanner::initScanner(seq, seqStart, seqEnd, isForward) + next()):
+ * `start` and `end` are 0-based coordinates inside sequence `seq` of the call, `end` inclusive; strand >= 0 = forward (the
+ * reference's block.strand > -1).  The block holds (end - start + 1) / 3 codons: codon j starts at start + 3 j on the forward
+ * strand, and is the complement strand read from end - 3 j downward on the reverse one; every run of 8 valid codons is a window,
+ * emitted if it passes the syncmer selection (or always, in dense mode).  A block shorter than 24 bases yields nothing.
+ * mtb_builder_add_blocks appends {value, taxids[seq]} for every window of every block; `taxids` as for mtb_builder_add_sequences.
+ * mtb_extract_blocks is the stage call (parity seam): the values in block order -- inside a block in the scanner's order, rising
+ * positions on the forward strand, from the block's end downward on the reverse one -- and, if block_of is not NULL, the index
+ * of the block each value came from.  *count = values the blocks yield; MTB_ERR_CAPACITY if that exceeds `cap` (nothing written).
+ * Both: kmer_format 2 only (MTB_ERR_UNSUPPORTED otherwise); n_blocks = 0 is legal; MTB_ERR_ARG, with the first offending block
+ * named by mtb_last_error(), for seq >= n_seqs, end < start or end beyond the sequence -- and the builder holds what it held. */
+typedef struct { uint32_t seq; int32_t strand; uint64_t start, end; } mtb_seq_block;
+mtb_status mtb_extract_blocks(mtb_ctx *, const mtb_params *, const char *bases, const uint64_t *offs, uint64_t n_seqs,
+                              const mtb_seq_block *blocks, uint64_t n_blocks,
+                              uint64_t *values, uint32_t *block_of /* may be NULL */, uint64_t cap, uint64_t *count);
+mtb_status mtb_builder_add_blocks(mtb_builder *, const char *bases, const uint64_t *offs, const int32_t *taxids, uint64_t n_seqs,
+                                  const mtb_seq_block *blocks, uint64_t n_blocks);
 /* the (value, info & info_mask) pairs of a resident index of the same device (updateDB's old database; bit 31 of legacy
  * databases is masked off as mergeTargetFiles does, IndexCreator.h:355, 400).  A sealed or packed index is brought to the flat
  * state as for mtb_index_download and held there, as a join holds its state, until its entries are copied: classification

@@ -24,6 +24,8 @@ match_dt = np.dtype([("qinfo", "<u8"), ("target_id", "<i4"), ("species_id", "<i4
 result_dt = np.dtype([("classification", "<i4"), ("score", "<f4"), ("qlen", "<i4"), ("qlen2", "<i4"),
                       ("is_classified", "u1"), ("flag", "u1"), ("n_taxcnt", "<u2"), ("taxcnt_off", "<u4")])
 
+block_dt = np.dtype([("seq", "<u4"), ("strand", "<i4"), ("start", "<u8"), ("end", "<u8")])      # mtb_seq_block: end inclusive, strand >= 0 = forward
+
 MTB_OK, MTB_ERR_ARG, MTB_ERR_IO, MTB_ERR_DEVICE, MTB_ERR_CAPACITY, MTB_ERR_OOM, MTB_ERR_UNSUPPORTED = range(7)
 
 
@@ -244,6 +246,26 @@ class Context:
         _chk(self.L.mtb_extract(self.h, C.byref(params), _p(bases), _p(offs), _p(bases2), _p(offs2), C.c_uint64(n),
                                 _p(out), C.c_uint64(cap), C.byref(cnt), _p(ql), _p(ql2)))
         return out[:cnt.value].copy(), ql, ql2
+
+    def extract_blocks(self, params, bases, offs, blocks, cap=None, want_block_of=True):
+        """mtb_extract_blocks: every block of `blocks` (a block_dt array over the sequences bases / offs) scanned in one frame on one
+        strand -> (values, block_of) in block order, inside a block in the scanner's order; block_of is None unless asked for.
+        A `cap` that turns out too small is replaced by the size the library reports."""
+        b = np.ascontiguousarray(bases, dtype=np.uint8)
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        k = np.ascontiguousarray(blocks, dtype=block_dt)
+        cap = max(16, int((k["end"] - k["start"] + np.uint64(1))[k["end"] >= k["start"]].sum()) // 3) if cap is None else int(cap)
+        while True:
+            v = np.zeros(cap, np.uint64)
+            bo = np.zeros(cap, np.uint32) if want_block_of else None
+            cnt = C.c_uint64()
+            st = self.L.mtb_extract_blocks(self.h, C.byref(params), _p(b), _p(o), C.c_uint64(len(o) - 1), _p(k), C.c_uint64(len(k)),
+                                           _p(v), _p(bo), C.c_uint64(cap), C.byref(cnt))
+            if st == MTB_ERR_CAPACITY and cnt.value > cap:
+                cap = cnt.value
+                continue
+            _chk(st)
+            return v[:cnt.value].copy(), (bo[:cnt.value].copy() if want_block_of else None)
 
     def sort_kmers(self, kmers):
         k = np.ascontiguousarray(kmers).copy()
@@ -489,7 +511,7 @@ BUILD_STAGES = ["keys", "sort_key", "sort_value", "heads_scan", "reduce", "total
 
 class Builder:
     """Database build / merge on the device (mtb_builder_*): the sort and the per-species LCA dedup of the reference's `build` /
-    `updateDB`.  Sequences are extracted in all six frames (no gene prediction)."""
+    `updateDB`.  add_sequences extracts in all six frames; add_blocks scans given blocks in one frame each (no gene prediction here)."""
 
     def __init__(self, ctx, h):
         self.ctx = ctx
@@ -502,6 +524,16 @@ class Builder:
         t = np.ascontiguousarray(taxids, dtype=np.int32)
         assert len(o) == len(t) + 1
         _chk(self.ctx.L.mtb_builder_add_sequences(self.h, _p(b), _p(o), _p(t), C.c_uint64(len(t))))
+
+    def add_blocks(self, bases, offs, taxids, blocks):
+        """mtb_builder_add_blocks: `blocks` (a block_dt array) of the sequences bases / offs / taxids, each scanned in one frame on one
+        strand -- the reference's build route, with blocks from a CDS annotation or a gene predictor"""
+        b = np.ascontiguousarray(bases, dtype=np.uint8)
+        o = np.ascontiguousarray(offs, dtype=np.uint64)
+        t = np.ascontiguousarray(taxids, dtype=np.int32)
+        k = np.ascontiguousarray(blocks, dtype=block_dt)
+        assert len(o) == len(t) + 1
+        _chk(self.ctx.L.mtb_builder_add_blocks(self.h, _p(b), _p(o), _p(t), C.c_uint64(len(t)), _p(k), C.c_uint64(len(k))))
 
     def add_records(self, values, taxids):
         v = np.ascontiguousarray(values, dtype=np.uint64)

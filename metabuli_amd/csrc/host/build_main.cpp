@@ -1,11 +1,16 @@
 /* mtb_build -- build, update or merge a database on the GPU (plain C++ over the C ABI, include/mtb.h).
  *
- *   mtb_build [--add-db OLDDB]... [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d]
+ *   mtb_build [--add-db OLDDB]... [--cds-info LIST] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d]
  *             GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB
  *
  * The sort + per-species LCA dedup of the reference's `build` (IndexCreator::createIndex) and the merge of `updateDB`
- * (mergeTargetFiles<DB_CREATION>): every FASTA record is extracted in ALL SIX FRAMES -- there is no gene prediction here, so the
- * result is not what the reference's Prodigal-guided `build` writes for the same genomes --, the first word of its header is looked up
+ * (mergeTargetFiles<DB_CREATION>).  Without --cds-info every FASTA record is extracted in ALL SIX FRAMES -- there is no gene
+ * prediction here, so the result is not what the reference's Prodigal-guided `build` writes for the same genomes.  With
+ * --cds-info LIST (a text file, one cds_from_genomic FASTA path per line, as the reference takes it) a record whose name has an
+ * entry in the annotation is cut into its CDS and the regions between them, each scanned in one frame (host/cds_info.h,
+ * mtb_builder_add_blocks): the reference's `build --cds-info LIST --mask 0` up to the departures cds_info.h lists; a record
+ * without an entry has no gene predictor to fall back to and is extracted in six frames, and the closing line says how many
+ * records took which route.  kmer_format 2 only.  The first word of a record's header is looked up
  * in the two-column map (sequence id, taxid), and the entries of every --add-db database are merged in.  GENOMES.fa may be `-` when
  * only --add-db arguments are given (a pure merge; the map is not read then).  OUTDB receives diffIdx, info, split, taxID_list,
  * db.parameters (mtb_index_write) and a copy of TAXONOMYDIR's *.dmp files in OUTDB/taxonomy, so that `mtb_classify ... OUTDB` runs
@@ -24,6 +29,7 @@
 
 #include "../../../include/mtb.h"
 #include "fastx.h"
+#include "cds_info.h"
 
 static void die(const std::string &m) { throw std::runtime_error(m); }
 static void chk(mtb_status s, const char *what) { if (s != MTB_OK) die(std::string(what) + ": " + mtb_last_error()); }
@@ -44,6 +50,7 @@ static void copy_file(const std::string &from, const std::string &to) {
 int main(int argc, char **argv) {
     try {
         std::vector<std::string> add_db, pos;
+        std::string cds_list;
         int split_num = 4096, device = 0;
         mtb_params par;
         mtb_default_params(&par);
@@ -52,6 +59,7 @@ int main(int argc, char **argv) {
             const std::string a = argv[i];
             auto val = [&]() -> std::string { if (i + 1 >= argc) die("flag " + a + " needs a value"); return argv[++i]; };
             if (a == "--add-db") add_db.push_back(val());
+            else if (a == "--cds-info") cds_list = val();
             else if (a == "--split-num") split_num = atoi(val().c_str());
             else if (a == "--syncmer") par.syncmer = atoi(val().c_str());
             else if (a == "--smer-len") par.smer_len = atoi(val().c_str());
@@ -61,13 +69,23 @@ int main(int argc, char **argv) {
             else pos.push_back(a);
         }
         if (pos.size() != 4) {
-            fprintf(stderr, "usage: mtb_build [--add-db OLDDB]... [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d] "
+            fprintf(stderr, "usage: mtb_build [--add-db OLDDB]... [--cds-info LIST] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d] "
                             "GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB\n");
             return 1;
         }
         const std::string genomes = pos[0], map_path = pos[1], taxdir = pos[2], outdb = pos[3];
         if (genomes == "-" && add_db.empty()) die("nothing to build: no genomes and no --add-db");
         if (split_num < 2) die("--split-num must be at least 2");
+        if (!cds_list.empty() && par.kmer_format != 2) die("--cds-info needs --kmer-format 2 (block extraction implements no other)");
+
+        mtbhost::CdsMap cds;
+        if (!cds_list.empty() && genomes != "-") {
+            mtbhost::cds_load_list(cds_list, &cds);
+            fprintf(stderr, "mtb_build: CDS annotation: %llu records, %llu CDS of %zu sequences (%llu pseudo, %llu hypothetical, %llu without a location, "
+                            "%llu locations without a protein_id skipped, %llu records with a two-digit accession version)\n",
+                    cds.stats.records, cds.stats.cds, cds.by_accession.size(), cds.stats.pseudo, cds.stats.hypothetical, cds.stats.no_location,
+                    cds.stats.orphan_location, cds.stats.two_digit_version);
+        }
 
         std::unordered_map<std::string, int32_t> seq2tax;
         if (genomes != "-") {
@@ -100,7 +118,7 @@ int main(int argc, char **argv) {
             fprintf(stderr, "mtb_build: %llu entries of %s\n", n_old, db.c_str());
         }
 
-        unsigned long long n_seqs = 0, n_bases = 0;
+        unsigned long long n_seqs = 0, n_bases = 0, n_by_blocks = 0, n_six_frames = 0, n_cds_single = 0, n_cds_joined = 0, n_noncds = 0;
         if (genomes != "-") {
             mtbhost::FastxReader rd(genomes, 4);
             mtbhost::FlatBatch batch;
@@ -124,8 +142,35 @@ int main(int argc, char **argv) {
                     if (it == seq2tax.end()) die("sequence " + id + " of " + genomes + " is not in " + map_path);
                     taxids[i] = it->second;
                 }
-                chk(mtb_builder_add_sequences(bld, batch.bases.data(), batch.offs.data(), taxids.data(), batch.size()), "mtb_builder_add_sequences");
                 n_seqs += batch.size(); n_bases += batch.offs[batch.size()];
+                if (cds_list.empty()) {
+                    chk(mtb_builder_add_sequences(bld, batch.bases.data(), batch.offs.data(), taxids.data(), batch.size()), "mtb_builder_add_sequences");
+                    continue;
+                }
+                /* records with an annotation entry -> blocks; the others -> six frames, as one compacted call */
+                mtbhost::CdsBlocks cb;
+                std::vector<char> plain_bases; std::vector<uint64_t> plain_offs(1, 0); std::vector<int32_t> plain_tax;
+                const size_t n0 = batch.size();
+                for (size_t i = 0; i < n0; i++) {
+                    std::string id = batch.name(i);
+                    id = id.substr(0, id.find_first_of(" \t"));
+                    const char *seq = batch.bases.data() + batch.offs[i];
+                    const uint64_t len = batch.offs[i + 1] - batch.offs[i];
+                    auto it = cds.by_accession.find(id);
+                    if (it == cds.by_accession.end()) {
+                        plain_bases.insert(plain_bases.end(), seq, seq + len); plain_offs.push_back(plain_bases.size()); plain_tax.push_back(taxids[i]);
+                        n_six_frames++;
+                    } else { mtbhost::cds_divide(it->second, id, seq, len, (uint32_t)i, &cb); n_by_blocks++; }
+                }
+                if (!plain_tax.empty())
+                    chk(mtb_builder_add_sequences(bld, plain_bases.data(), plain_offs.data(), plain_tax.data(), plain_tax.size()), "mtb_builder_add_sequences");
+                /* the joined CDS go behind the genomes as sequences of the same call */
+                mtbhost::cds_finish_extras(&cb, (uint32_t)n0);
+                batch.bases.append(cb.extra_bases.data(), cb.extra_bases.data() + cb.extra_bases.size());
+                for (size_t k = 0; k < cb.extra_lens.size(); k++) { batch.offs.push_back(batch.offs[batch.offs.size() - 1] + cb.extra_lens[k]); taxids.push_back(taxids[cb.extra_owner[k]]); }
+                if (!cb.blocks.empty())
+                    chk(mtb_builder_add_blocks(bld, batch.bases.data(), batch.offs.data(), taxids.data(), taxids.size(), cb.blocks.data(), cb.blocks.size()), "mtb_builder_add_blocks");
+                n_cds_single += cb.n_cds_single; n_cds_joined += cb.n_cds_joined; n_noncds += cb.n_noncds;
             }
         }
         const unsigned long long n_rec = mtb_builder_num_records(bld);
@@ -143,8 +188,13 @@ int main(int argc, char **argv) {
             closedir(d);
             for (const std::string &n : names) copy_file(taxdir + "/" + n, otax + "/" + n);
         }
-        fprintf(stderr, "mtb_build: %llu sequences (%llu bases), %llu records -> %llu entries in %s (six-frame extraction, no gene prediction)\n",
-                n_seqs, n_bases, n_rec, (unsigned long long)mtb_index_num_targets(ix), outdb.c_str());
+        if (cds_list.empty())
+            fprintf(stderr, "mtb_build: %llu sequences (%llu bases), %llu records -> %llu entries in %s (six-frame extraction, no gene prediction)\n",
+                    n_seqs, n_bases, n_rec, (unsigned long long)mtb_index_num_targets(ix), outdb.c_str());
+        else
+            fprintf(stderr, "mtb_build: %llu sequences (%llu bases), %llu records -> %llu entries in %s (CDS annotation: %llu sequences by blocks -- %llu CDS, "
+                            "%llu joined CDS, %llu non-CDS regions --, %llu sequences without a CDS entry in six frames; no gene prediction, no masking)\n",
+                    n_seqs, n_bases, n_rec, (unsigned long long)mtb_index_num_targets(ix), outdb.c_str(), n_by_blocks, n_cds_single, n_cds_joined, n_noncds, n_six_frames);
         mtb_index_close(ix);
         mtb_builder_destroy(bld);
         mtb_ctx_destroy(ctx);

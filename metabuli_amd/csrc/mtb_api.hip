@@ -19,6 +19,7 @@
 #include "../../include/mtb.h"
 #include "host_db.h"
 #include "kernels_extract.h"
+#include "kernels_extract_blocks.h"
 #include "kernels_index.h"
 #include "kernels_join.h"
 #include "kernels_build.h"
@@ -3553,6 +3554,88 @@ mtb_status mtb_extract_targets(mtb_ctx *c, const mtb_params *p, const char *geno
 } // extern "C"
 
 /* ------------------------------------------------------------------ */
+/* block scan (kernels_extract_blocks.h)                               */
+/* ------------------------------------------------------------------ */
+static mtb_status block_scan_params(const mtb_params *p) {
+    if (p->kmer_format != 2) return fail(MTB_ERR_UNSUPPORTED, "block extraction implements kmer_format 2 only (what the reference's build passes to IndexCreator)");
+    if (p->syncmer && (p->smer_len < 1 || p->smer_len > 8)) return fail(MTB_ERR_ARG, "smer_len out of range");
+    return MTB_OK;
+}
+/* every block inside its sequence; the message names the first one that is not */
+static mtb_status check_blocks(const uint64_t *offs, uint64_t n_seqs, const mtb_seq_block *blocks, uint64_t n_blocks) {
+    if (n_blocks >= (1ull << 32)) return fail(MTB_ERR_ARG, "2^32 or more blocks in one call");
+    for (uint64_t i = 0; i < n_seqs; i++)
+        if (offs[i + 1] < offs[i]) return fail(MTB_ERR_ARG, "offs must not decrease (sequence " + std::to_string(i) + ")");
+    for (uint64_t i = 0; i < n_blocks; i++) {
+        const mtb_seq_block &k = blocks[i];
+        const std::string who = "block " + std::to_string(i) + ": ";
+        if (k.seq >= n_seqs) return fail(MTB_ERR_ARG, who + "seq " + std::to_string(k.seq) + " of " + std::to_string(n_seqs) + " sequences");
+        if (k.end < k.start) return fail(MTB_ERR_ARG, who + "end " + std::to_string(k.end) + " before start " + std::to_string(k.start));
+        const uint64_t len = offs[k.seq + 1] - offs[k.seq];
+        if (k.end >= len) return fail(MTB_ERR_ARG, who + "end " + std::to_string(k.end) + " beyond sequence " + std::to_string(k.seq) + " of " + std::to_string(len) + " bases");
+    }
+    return MTB_OK;
+}
+struct BlockScan { BlockScanArgs a; uint64_t *d_base = nullptr; uint64_t total = 0; uint32_t grid = 0; };
+/* checks, uploads, piece table, count launch, offsets: leaves what the emit launch needs.  total = records the blocks yield. */
+static mtb_status dev_count_blocks(mtb_ctx *c, const mtb_params *p, const char *bases, const uint64_t *offs, uint64_t n_seqs,
+                                   const mtb_seq_block *blocks, uint64_t n_blocks, BlockScan *bs) {
+    *bs = BlockScan();
+    STCHK(check_blocks(offs, n_seqs, blocks, n_blocks));
+    if (n_blocks == 0) return MTB_OK;
+    mtb_params q = *p; q.seq_mode = 3;
+    char *d_b, *d_b2; uint64_t *d_o, *d_o2; uint64_t nb;
+    STCHK(upload_reads(c, &q, bases, offs, nullptr, nullptr, n_seqs, &d_b, &d_o, &d_b2, &d_o2, &nb));
+    mtb_seq_block *d_blk; uint32_t *d_np; uint64_t *d_ps, *d_ws;
+    STCHK(ensure(c, "blk", n_blocks, &d_blk, BUF_IO)); STCHK(ensure(c, "blk_np", n_blocks, &d_np)); STCHK(ensure(c, "blk_ps", n_blocks + 1, &d_ps));
+    STCHK(ensure(c, "scanws", scan_ws_elems(n_blocks + 1), &d_ws));
+    STCHK(h2d(c, d_blk, blocks, n_blocks * sizeof(mtb_seq_block)));
+    hipLaunchKernelGGL(k_block_pieces, dim3((uint32_t)((n_blocks + 255) / 256)), dim3(256), 0, c->stream, (const mtb_seq_block *)d_blk, n_blocks, d_np);
+    scan_launch<uint32_t, uint64_t, false>(c->stream, d_np, n_blocks, true, d_ps, d_ws);
+    HIPCHK(hipGetLastError());
+    uint64_t n_pieces = 0;
+    STCHK(d2h(c, &n_pieces, d_ps + n_blocks, 8));
+    if (n_pieces == 0) return MTB_OK;
+    uint32_t *d_cnt;
+    STCHK(ensure(c, "blk_cnt", n_pieces, &d_cnt)); STCHK(ensure(c, "blk_base", n_pieces + 1, &bs->d_base));
+    STCHK(ensure(c, "scanws", scan_ws_elems(n_pieces + 1), &d_ws));
+    bs->a = BlockScanArgs{d_b, d_o, d_blk, n_blocks, d_ps, n_pieces, p->syncmer, p->smer_len};
+    bs->grid = (uint32_t)std::min<uint64_t>(n_pieces, 256ull * 256);
+    hipLaunchKernelGGL((k_extract_blocks<0>), dim3(bs->grid), dim3(64), 0, c->stream, bs->a, c->d_tabs, d_cnt, (const uint64_t *)nullptr,
+                       (const int32_t *)nullptr, (mtb_kmer *)nullptr, (uint64_t *)nullptr, (uint32_t *)nullptr);
+    scan_launch<uint32_t, uint64_t, false>(c->stream, d_cnt, n_pieces, true, bs->d_base, d_ws);
+    HIPCHK(hipGetLastError());
+    STCHK(d2h(c, &bs->total, bs->d_base + n_pieces, 8));
+    return MTB_OK;
+}
+
+extern "C" {
+
+mtb_status mtb_extract_blocks(mtb_ctx *c, const mtb_params *p, const char *bases, const uint64_t *offs, uint64_t n_seqs,
+                              const mtb_seq_block *blocks, uint64_t n_blocks, uint64_t *values, uint32_t *block_of, uint64_t cap, uint64_t *count) {
+    if (!c || !p || !count || (n_seqs && (!bases || !offs)) || (n_blocks && !blocks) || (cap && !values)) return fail(MTB_ERR_ARG, "NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    *count = 0;
+    STCHK(block_scan_params(p));
+    BlockScan bs;
+    STCHK(dev_count_blocks(c, p, bases, offs, n_seqs, blocks, n_blocks, &bs));
+    *count = bs.total;
+    if (bs.total > cap) return fail(MTB_ERR_CAPACITY, "value buffer too small");
+    if (bs.total == 0) return MTB_OK;
+    uint64_t *d_v; uint32_t *d_bo = nullptr;
+    STCHK(ensure(c, "blk_val", bs.total, &d_v, BUF_IO));
+    if (block_of) STCHK(ensure(c, "blk_of", bs.total, &d_bo, BUF_IO));
+    hipLaunchKernelGGL((k_extract_blocks<2>), dim3(bs.grid), dim3(64), 0, c->stream, bs.a, c->d_tabs, (uint32_t *)nullptr, (const uint64_t *)bs.d_base,
+                       (const int32_t *)nullptr, (mtb_kmer *)nullptr, d_v, d_bo);
+    HIPCHK(hipGetLastError());
+    STCHK(d2h(c, values, d_v, bs.total * 8));
+    if (block_of) STCHK(d2h(c, block_of, d_bo, bs.total * 4));
+    return MTB_OK;
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------------------ */
 /* database build / merge (kernels_build.h)                            */
 /* ------------------------------------------------------------------ */
 struct mtb_builder {
@@ -3677,6 +3760,29 @@ mtb_status mtb_builder_add_sequences(mtb_builder *b, const char *bases, const ui
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     b->n += ex.nk;
+    return MTB_OK;
+}
+
+mtb_status mtb_builder_add_blocks(mtb_builder *b, const char *bases, const uint64_t *offs, const int32_t *taxids, uint64_t n_seqs,
+                                  const mtb_seq_block *blocks, uint64_t n_blocks) {
+    if (!b || (n_seqs && (!bases || !offs || !taxids)) || (n_blocks && !blocks)) return fail(MTB_ERR_ARG, "NULL argument");
+    mtb_ctx *c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    STCHK(block_scan_params(&b->params));
+    STCHK(builder_check_taxids(b, taxids, n_seqs));
+    BlockScan bs;
+    STCHK(dev_count_blocks(c, &b->params, bases, offs, n_seqs, blocks, n_blocks, &bs));
+    if (bs.total == 0) return MTB_OK;
+    STCHK(builder_reserve(b, bs.total));
+    int32_t *d_t;
+    STCHK(ensure(c, "btax", n_seqs, &d_t, BUF_IO));
+    STCHK(h2d(c, d_t, taxids, n_seqs * 4));
+    /* the records go straight behind the builder's list: no intermediate metamer list, no append pass */
+    hipLaunchKernelGGL((k_extract_blocks<1>), dim3(bs.grid), dim3(64), 0, c->stream, bs.a, c->d_tabs, (uint32_t *)nullptr, (const uint64_t *)bs.d_base,
+                       (const int32_t *)d_t, b->d_rec + b->n, (uint64_t *)nullptr, (uint32_t *)nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    b->n += bs.total;
     return MTB_OK;
 }
 

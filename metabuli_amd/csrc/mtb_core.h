@@ -229,6 +229,32 @@ MTB_HD bool mtb_window_metamer(const uint8_t *cod, int syncmer, int smer_len, ui
 }
 
 /* ------------------------------------------------------------------ */
+/* Block scan: one frame of one strand over [start, end] of a sequence */
+/* ------------------------------------------------------------------ */
+/* KmerScanner::initScanner(seq, seqStart, seqEnd, isForward) + MetamerScanner::next / SyncmerScanner::next (KmerScanner.h:56-117,
+ * SyncmerScanner.h:36-101) as IndexCreator drives them over a sequence block (KmerExtractor::extractTargetKmers,
+ * KmerExtractor.cpp:407-426): the block holds aaLen = (end - start + 1) / 3 codons, codon j starts at start + 3 j on the forward
+ * strand and is the complement strand read from end - 3 j downward on the reverse one; window p covers codons p .. p + 7 and is
+ * emitted iff mtb_window_metamer says so.  Both coordinates are 0-based inside the sequence, `end` is inclusive.  kmer_format 2
+ * only (what build.cpp:94 hands IndexCreator).  A six-frame scan's frame 0 / frame 3 over the block's codons is the same thing. */
+#define MTB_BLOCK_PIECE_WINDOWS 4096     /* windows of a block one wavefront takes (kernels_extract_blocks.h) */
+MTB_HD uint64_t mtb_block_codons(uint64_t start, uint64_t end) { return end < start ? 0ull : (end - start + 1) / 3; }
+MTB_HD uint64_t mtb_block_windows(uint64_t start, uint64_t end) { const uint64_t a = mtb_block_codons(start, end); return a >= 8 ? a - 7 : 0ull; }
+MTB_HD uint64_t mtb_block_pieces(uint64_t start, uint64_t end) { return (mtb_block_windows(start, end) + MTB_BLOCK_PIECE_WINDOWS - 1) / MTB_BLOCK_PIECE_WINDOWS; }
+/* forward coordinate of the first base (in reading direction) of codon j */
+MTB_HD int64_t mtb_block_codon_ci(uint64_t start, uint64_t end, uint64_t j, bool fwd) { return fwd ? (int64_t)(start + 3 * j) : (int64_t)(end - 3 * j); }
+MTB_HD uint8_t mtb_block_codon(const mtb_tables *t, const char *seq, uint64_t start, uint64_t end, uint64_t j, bool fwd) {
+    return mtb_codon_byte(t, seq, mtb_block_codon_ci(start, end, j, fwd), fwd);
+}
+/* window p < mtb_block_windows(start, end), straight from the bases (the kernel stages the codon bytes of 64 windows in LDS instead) */
+MTB_HD bool mtb_block_window(const mtb_tables *t, const char *seq, uint64_t start, uint64_t end, uint64_t p, bool fwd, int syncmer, int smer_len, uint64_t *value) {
+    uint8_t cod[8];
+MTB_UNROLL
+    for (int i = 0; i < 8; i++) cod[i] = mtb_block_codon(t, seq, start, end, p + (uint64_t)i, fwd);
+    return mtb_window_metamer(cod, syncmer, smer_len, value);
+}
+
+/* ------------------------------------------------------------------ */
 /* Join: Hamming arithmetic on 24-bit codon-id strings                  */
 /* ------------------------------------------------------------------ */
 typedef struct { uint32_t row[8]; uint32_t qdna; } mtb_qrows;   /* row[i]: hamming row of query codon i (i=0 is the LSB codon) */
