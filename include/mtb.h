@@ -487,7 +487,8 @@ mtb_status mtb_extract_targets(mtb_ctx *, const mtb_params *, const char *genome
  * A reduced-alphabet OLD database never reaches mtb_builder_add_index, because mtb_index_open refuses to open it.
  * Memory: the records are one device array of 16 B each that grows by half when full (allocate, copy, free), so while it grows
  * both copies exist: up to 2.5 x the list, 40 B per record held, and MTB_ERR_OOM comes that much before HBM is full.  finish
- * needs the list plus two sort buffers of the same size (48 B per record) plus the output.  Callers that know the total add the
+ * needs the list plus two sort buffers of the same size (48 B per record) plus the output; what does not fit one builder, or holds
+ * 2^32 records or more, is built in parts and merged by mtb_merge_databases (below).  Callers that know the total add the
  * largest part first; each add_sequences call costs an upload, a two-pass extraction and a few stream synchronisations, so
  * pass many sequences per call (mtb_build passes about 64 M bases at a time). */
 typedef struct mtb_builder mtb_builder;
@@ -519,10 +520,15 @@ mtb_status mtb_builder_add_blocks(mtb_builder *, const char *bases, const uint64
  * kmer_format / syncmer / smer_len differ from the builder's. */
 mtb_status mtb_builder_add_index(mtb_builder *, mtb_index *);
 uint64_t   mtb_builder_num_records(const mtb_builder *);
+/* How many records this builder can hold AND finish with the device memory that is free now (plus what the builder and the
+ * context's workspace already hold): 72 B per record -- the list, finish's two sort buffers, head flags and positions, the output
+ * entries -- capped below 2^32.  What a caller that builds in parts (mtb_build --max-records) spills at. */
+mtb_status mtb_builder_capacity(const mtb_builder *, uint64_t *max_records);
 /* An ordinary owning index (flat state, directory built, skip_redundancy = 1) for mtb_classify_batch*, mtb_index_write,
  * mtb_index_seal, mtb_index_clone, mtb_index_download; the builder is empty afterwards and may be reused.  MTB_ERR_ARG: no
- * records, or 2^32 or more of them (the device sort's limit: build in parts and merge the parts).  The context's batch
- * workspace is released on the way (the sort needs the room). */
+ * records, or 2^32 or more of them (the device sort's limit: write the parts with mtb_index_write and merge them with
+ * mtb_merge_databases, as `mtb_build --max-records` does).  The context's batch workspace is released on the way (the sort needs
+ * the room). */
 mtb_status mtb_builder_finish(mtb_builder *, mtb_index **out);
 void       mtb_builder_destroy(mtb_builder *);
 /* Device time of the last mtb_builder_finish by stage, and what it saw.  Part of the ABI on purpose, and small: it is the only
@@ -537,6 +543,43 @@ typedef struct {
     uint64_t n_records, n_entries, n_long_groups;     /* input records, output entries, groups a whole wavefront folded */
 } mtb_build_stats;
 mtb_status mtb_builder_last_finish_stats(const mtb_builder *, mtb_build_stats *out);
+
+/* ---- streamed merge of databases: beyond 2^32 records, beyond one builder's HBM --------------------------------------
+ * mergeTargetFiles<DB_CREATION> (IndexCreator.h:323-472: the reference writes one partial index per RAM-sized batch and streams the
+ * sorted partial files into the final one).  The databases `dbdirs` are merged into `outdir` (an existing directory) one VALUE RANGE
+ * at a time; a range is never resident beyond its turn and nothing that is already sorted is sorted again.  Per range: every
+ * input's slice is decoded from its last `split` checkpoint at or below the range to its first at or above it and trimmed to the
+ * range, turned into {value, (species, taxid)} records under the taxonomy of `taxonomy_dir`, the k sorted lists are merged by a
+ * pairwise tree of merge-path merges between two buffers (kernels_merge.h), the builder's per-species LCA dedup folds the groups,
+ * and the entries are delta-coded and appended to outdir's files.  The ranges come from the inputs' split tables and file sizes
+ * alone (metabuli_amd/csrc/host/merge_plan.h): bounds are amino-acid parts of checkpoints, the entries a range reads -- over all
+ * inputs, between the enclosing checkpoints -- stay at or below max_range_records and below 2^32.
+ * Result: diffIdx, info, split, taxID_list and db.parameters are byte-identical to what mtb_builder_create(taxonomy_dir),
+ * mtb_builder_add_index of every input, mtb_builder_finish and mtb_index_write(outdir, split_num) write, whatever
+ * max_range_records is (per-part dedup followed by a merge dedup is the global one: the LCA fold is associative and commutative).
+ * Inputs: `params` fixes kmer_format, syncmer and smer_len; an input whose db.parameters says otherwise is MTB_ERR_ARG, a
+ * reduced-alphabet one MTB_ERR_UNSUPPORTED; bit 31 of the info entries of legacy inputs (Skip_redundancy 0) is masked off.  An
+ * info id the taxonomy does not know (after merged.dmp aliasing) is MTB_ERR_ARG and named by mtb_last_error().  A slice that does
+ * not ascend in (value, species) under THIS taxonomy (its database was built with another one) is radix-sorted before the merge
+ * (n_resorted_slices; needs 16 B per record of the slice on top of the budget below).
+ * max_range_records = 0: derived from free HBM as (free - 4 GiB) / MTB_MERGE_BYTES_PER_RECORD, where per record of a range the
+ * merge holds 2 x 16 B (the two merge buffers; a decoded slice, 12 B per entry, lies in the one not yet written), 8 B (head flags
+ * and scanned positions), 12 B (the range's output entries) and 4 B for the long-group list and scan workspace = 56 B; the 4 GiB
+ * are the decode chunks, the writer's slice buffers and the taxonomy.  MTB_ERR_CAPACITY: one step between neighbouring range
+ * bounds does not fit max_range_records; the message gives the number of records it needs.
+ * db.parameters is removed from outdir first and written last: after any failure outdir cannot be opened as a database.
+ * stats (may be NULL): entries read / written, ranges, the largest range's records, slices that had to be sorted, and host-clock
+ * milliseconds by stage (each stage ends with a stream synchronisation): slices read + decoded + keyed, merged, deduplicated,
+ * coded + written, the split table located (re-decoding the written diffIdx from per-slice restart records), the whole call. */
+#define MTB_MERGE_BYTES_PER_RECORD 56
+typedef struct { uint64_t n_input_entries, n_entries, n_ranges, max_range_records_used, n_resorted_slices;
+                 float ms_read_decode, ms_merge, ms_reduce, ms_encode_write, ms_split, ms_total; } mtb_merge_stats;
+mtb_status mtb_merge_databases(mtb_ctx *, const char *const *dbdirs, uint32_t n_dbs, const char *taxonomy_dir,
+                               const mtb_params *, const char *outdir, int split_num,
+                               uint64_t max_range_records /* 0: from free HBM */, mtb_merge_stats *stats /* may be NULL */);
+/* stage call (parity seam): two host lists of {value, qinfo}, each ascending in (value, qinfo) -> their merge in `out`
+ * (n_a + n_b records; equal records of a come first).  The tile of the merge kernel is 2048 records. */
+mtb_status mtb_merge_sorted(mtb_ctx *, const mtb_kmer *a, uint64_t n_a, const mtb_kmer *b, uint64_t n_b, mtb_kmer *out);
 
 #ifdef __cplusplus
 }

@@ -189,5 +189,16 @@ private:
     Engine &eng; LocalParameters par; std::map<int, unsigned> taxCounts;
 };
 
+/* mergeTargetFiles<DB_CREATION> (IndexCreator.h:323-472) over whole databases: mtb_merge_databases -- streamed by value range, no
+ * 2^32-record limit; maxRangeRecords = 0 sizes the ranges from free HBM.  Throws like every call of this header. */
+inline mtb_merge_stats mergeDatabases(mtb_ctx *ctx, const std::vector<std::string> &dbDirs, const std::string &taxonomyDir, const LocalParameters &par,
+                                      const std::string &outDir, int splitNum = 4096, uint64_t maxRangeRecords = 0) {
+    std::vector<const char *> dirs;
+    for (const std::string &d : dbDirs) dirs.push_back(d.c_str());
+    mtb_merge_stats st;
+    check(mtb_merge_databases(ctx, dirs.data(), (uint32_t)dirs.size(), taxonomyDir.c_str(), &par, outDir.c_str(), splitNum, maxRangeRecords, &st));
+    return st;
+}
+
 } // namespace mtb
 #endif

@@ -235,6 +235,22 @@ class Context:
         _chk(self.L.mtb_builder_create(self.h, taxonomy_dir.encode(), C.byref(params), C.byref(h)))
         return Builder(self, h)
 
+    def merge_databases(self, dbdirs, taxonomy_dir, params, outdir, split_num=4096, max_range_records=0):
+        """mtb_merge_databases: the databases `dbdirs` streamed into the existing directory `outdir`, one value range at a time (no
+        2^32-record limit, nothing re-sorted); max_range_records = 0 sizes the ranges from free HBM.  -> the call's statistics"""
+        dirs = (C.c_char_p * max(len(dbdirs), 1))(*[d.encode() for d in dbdirs])
+        s = MergeStats()
+        _chk(self.L.mtb_merge_databases(self.h, dirs, C.c_uint32(len(dbdirs)), taxonomy_dir.encode(), C.byref(params), outdir.encode(),
+                                        C.c_int(split_num), C.c_uint64(int(max_range_records)), C.byref(s)))
+        return {name: (float(getattr(s, name)) if name.startswith("ms_") else int(getattr(s, name))) for name, _ in MergeStats._fields_}
+
+    def merge_sorted(self, a, b):
+        """mtb_merge_sorted (stage call of the merge kernels): two kmer_dt lists, each ascending in (value, qinfo) -> their merge"""
+        a = np.ascontiguousarray(a, dtype=kmer_dt); b = np.ascontiguousarray(b, dtype=kmer_dt)
+        out = np.zeros(len(a) + len(b), kmer_dt)
+        _chk(self.L.mtb_merge_sorted(self.h, _p(a), C.c_uint64(len(a)), _p(b), C.c_uint64(len(b)), _p(out)))
+        return out
+
     # ---- stages (host buffers) ----
     def extract(self, params, bases, offs, bases2=None, offs2=None, cap=None):
         n = len(offs) - 1
@@ -505,6 +521,14 @@ class Context:
 class BuildStats(C.Structure):
     _fields_ = [("ms", C.c_float * 6), ("n_records", C.c_uint64), ("n_entries", C.c_uint64), ("n_long_groups", C.c_uint64)]
 
+
+class MergeStats(C.Structure):
+    _fields_ = [("n_input_entries", C.c_uint64), ("n_entries", C.c_uint64), ("n_ranges", C.c_uint64), ("max_range_records_used", C.c_uint64),
+                ("n_resorted_slices", C.c_uint64), ("ms_read_decode", C.c_float), ("ms_merge", C.c_float), ("ms_reduce", C.c_float),
+                ("ms_encode_write", C.c_float), ("ms_split", C.c_float), ("ms_total", C.c_float)]
+
+
+MERGE_TILE = 2048          # records per tile of the merge kernel (MTB_MERGE_TILE, kernels_merge.h)
 
 BUILD_STAGES = ["keys", "sort_key", "sort_value", "heads_scan", "reduce", "total"]
 

@@ -1,7 +1,7 @@
 /* mtb_build -- build, update or merge a database on the GPU (plain C++ over the C ABI, include/mtb.h).
  *
- *   mtb_build [--add-db OLDDB]... [--cds-info LIST] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d]
- *             GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB
+ *   mtb_build [--add-db OLDDB]... [--cds-info LIST] [--max-records N] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2]
+ *             [--device d] GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB
  *
  * The sort + per-species LCA dedup of the reference's `build` (IndexCreator::createIndex) and the merge of `updateDB`
  * (mergeTargetFiles<DB_CREATION>).  Without --cds-info every FASTA record is extracted in ALL SIX FRAMES -- there is no gene
@@ -14,9 +14,15 @@
  * in the two-column map (sequence id, taxid), and the entries of every --add-db database are merged in.  GENOMES.fa may be `-` when
  * only --add-db arguments are given (a pure merge; the map is not read then).  OUTDB receives diffIdx, info, split, taxID_list,
  * db.parameters (mtb_index_write) and a copy of TAXONOMYDIR's *.dmp files in OUTDB/taxonomy, so that `mtb_classify ... OUTDB` runs
- * with no further arguments. */
+ * with no further arguments.
+ * A build larger than one builder (IndexCreator::createIndex writes one partial index per RAM-sized batch and mergeTargetFiles
+ * streams them together): when the builder holds --max-records N records (default: what mtb_builder_capacity reports for this
+ * device, below 2^32) it is finished and written to OUTDB/tmp_parts/part_K, and at the end the parts and every --add-db database --
+ * which then never enter a builder -- are merged by mtb_merge_databases, one value range at a time; tmp_parts is removed.  A pure
+ * merge (GENOMES `-`) always takes that route.  A build that fits takes the in-memory one; the files are the same either way. */
 #include <dirent.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <cstdio>
@@ -33,6 +39,25 @@
 
 static void die(const std::string &m) { throw std::runtime_error(m); }
 static void chk(mtb_status s, const char *what) { if (s != MTB_OK) die(std::string(what) + ": " + mtb_last_error()); }
+
+static void remove_tree(const std::string &dir) {
+    DIR *d = opendir(dir.c_str());
+    if (!d) return;
+    std::vector<std::string> names;
+    while (struct dirent *e = readdir(d)) { const std::string n = e->d_name; if (n != "." && n != "..") names.push_back(n); }
+    closedir(d);
+    for (const std::string &n : names) {
+        const std::string p = dir + "/" + n;
+        struct stat st;
+        if (lstat(p.c_str(), &st) == 0 && S_ISDIR(st.st_mode)) remove_tree(p); else unlink(p.c_str());
+    }
+    rmdir(dir.c_str());
+}
+static unsigned long long entries_of(const std::string &db) {
+    struct stat st;
+    if (stat((db + "/info").c_str(), &st) != 0) die("cannot open " + db + "/info");
+    return (unsigned long long)st.st_size / 4;
+}
 
 static void copy_file(const std::string &from, const std::string &to) {
     struct stat a, b;
@@ -52,6 +77,7 @@ int main(int argc, char **argv) {
         std::vector<std::string> add_db, pos;
         std::string cds_list;
         int split_num = 4096, device = 0;
+        unsigned long long max_records = 0;          /* 0: from the device */
         mtb_params par;
         mtb_default_params(&par);
         par.kmer_format = 2; par.syncmer = 0; par.smer_len = 5; par.skip_redundancy = 1;
@@ -61,6 +87,7 @@ int main(int argc, char **argv) {
             if (a == "--add-db") add_db.push_back(val());
             else if (a == "--cds-info") cds_list = val();
             else if (a == "--split-num") split_num = atoi(val().c_str());
+            else if (a == "--max-records") { max_records = strtoull(val().c_str(), nullptr, 10); if (max_records == 0) die("--max-records must be at least 1"); }
             else if (a == "--syncmer") par.syncmer = atoi(val().c_str());
             else if (a == "--smer-len") par.smer_len = atoi(val().c_str());
             else if (a == "--kmer-format") par.kmer_format = atoi(val().c_str());
@@ -69,7 +96,7 @@ int main(int argc, char **argv) {
             else pos.push_back(a);
         }
         if (pos.size() != 4) {
-            fprintf(stderr, "usage: mtb_build [--add-db OLDDB]... [--cds-info LIST] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d] "
+            fprintf(stderr, "usage: mtb_build [--add-db OLDDB]... [--cds-info LIST] [--max-records N] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d] "
                             "GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB\n");
             return 1;
         }
@@ -106,17 +133,27 @@ int main(int argc, char **argv) {
         mtb_builder *bld = nullptr;
         chk(mtb_builder_create(ctx, taxdir.c_str(), &par, &bld), "mtb_builder_create");
 
-        for (const std::string &db : add_db) {
-            mtb_params q = par;
-            mtb_index *old = nullptr;
-            chk(mtb_index_open(ctx, db.c_str(), taxdir.c_str(), &q, &old), ("open " + db).c_str());
-            const mtb_status s = mtb_builder_add_index(bld, old);
+        const bool max_given = max_records != 0;
+        if (!max_given) { uint64_t cap = 0; chk(mtb_builder_capacity(bld, &cap), "mtb_builder_capacity"); max_records = std::max<uint64_t>(cap - cap / 4, 1); }      /* a batch may overshoot */
+        if (max_records >= (1ull << 32)) max_records = (1ull << 32) - 1;
+        mkdir(outdb.c_str(), 0755);
+        const std::string parts_dir = outdb + "/tmp_parts";
+        std::vector<std::string> parts;
+        unsigned long long n_rec = 0;
+        /* the builder's records become a database of their own */
+        auto spill = [&]() {
+            if (parts.empty()) { remove_tree(parts_dir); mkdir(parts_dir.c_str(), 0755); }
+            const std::string pd = parts_dir + "/part_" + std::to_string(parts.size());
+            mkdir(pd.c_str(), 0755);
+            n_rec += mtb_builder_num_records(bld);
+            mtb_index *part = nullptr;
+            chk(mtb_builder_finish(bld, &part), "mtb_builder_finish");
+            const mtb_status s = mtb_index_write(part, pd.c_str(), split_num);
             const std::string err = s == MTB_OK ? std::string() : std::string(mtb_last_error());
-            const unsigned long long n_old = mtb_index_num_targets(old);
-            mtb_index_close(old);
-            if (s != MTB_OK) die("add " + db + ": " + err);
-            fprintf(stderr, "mtb_build: %llu entries of %s\n", n_old, db.c_str());
-        }
+            mtb_index_close(part);
+            if (s != MTB_OK) die("write " + pd + ": " + err);
+            parts.push_back(pd);
+        };
 
         unsigned long long n_seqs = 0, n_bases = 0, n_by_blocks = 0, n_six_frames = 0, n_cds_single = 0, n_cds_joined = 0, n_noncds = 0;
         if (genomes != "-") {
@@ -125,10 +162,10 @@ int main(int argc, char **argv) {
             std::vector<int32_t> taxids;
             /* one add_sequences call (an upload, a two-pass extraction, a few stream synchronisations) per ~64 M bases, however many
              * records that is: a contig-level assembly set must not become millions of tiny GPU round trips */
-            const size_t BATCH_BASES = 64u << 20, MAX_RECORDS = 1u << 16;
+            const size_t BATCH_BASES = (size_t)std::min<unsigned long long>(64u << 20, std::max<unsigned long long>(max_records / 4, 1)), MAX_RECORDS = 1u << 16;      /* a batch yields up to two records per base */
             for (;;) {
                 batch.clear();
-                size_t ask = 64;
+                size_t ask = BATCH_BASES < (64u << 20) ? 1 : 64;      /* a small --max-records: feel the way, a record at a time */
                 while (batch.bases.size() < BATCH_BASES && rd.next_batch(ask, batch)) {
                     const size_t avg = batch.bases.size() / batch.size() + 1;
                     ask = batch.bases.size() < BATCH_BASES ? std::min<size_t>(std::max<size_t>((BATCH_BASES - batch.bases.size()) / avg, 1), MAX_RECORDS) : 0;
@@ -145,6 +182,7 @@ int main(int argc, char **argv) {
                 n_seqs += batch.size(); n_bases += batch.offs[batch.size()];
                 if (cds_list.empty()) {
                     chk(mtb_builder_add_sequences(bld, batch.bases.data(), batch.offs.data(), taxids.data(), batch.size()), "mtb_builder_add_sequences");
+                    if (mtb_builder_num_records(bld) >= max_records) spill();
                     continue;
                 }
                 /* records with an annotation entry -> blocks; the others -> six frames, as one compacted call */
@@ -171,13 +209,42 @@ int main(int argc, char **argv) {
                 if (!cb.blocks.empty())
                     chk(mtb_builder_add_blocks(bld, batch.bases.data(), batch.offs.data(), taxids.data(), taxids.size(), cb.blocks.data(), cb.blocks.size()), "mtb_builder_add_blocks");
                 n_cds_single += cb.n_cds_single; n_cds_joined += cb.n_cds_joined; n_noncds += cb.n_noncds;
+                if (mtb_builder_num_records(bld) >= max_records) spill();
             }
         }
-        const unsigned long long n_rec = mtb_builder_num_records(bld);
-        mtb_index *ix = nullptr;
-        chk(mtb_builder_finish(bld, &ix), "mtb_builder_finish");
-        mkdir(outdb.c_str(), 0755);
-        chk(mtb_index_write(ix, outdb.c_str(), split_num), "mtb_index_write");
+        unsigned long long n_old = 0, n_entries = 0;
+        for (const std::string &db : add_db) n_old += entries_of(db);
+        const bool streamed = genomes == "-" || !parts.empty() || mtb_builder_num_records(bld) + n_old > max_records;
+        mtb_merge_stats ms = mtb_merge_stats();
+        if (!streamed) {
+            for (const std::string &db : add_db) {
+                mtb_params q = par;
+                mtb_index *old = nullptr;
+                chk(mtb_index_open(ctx, db.c_str(), taxdir.c_str(), &q, &old), ("open " + db).c_str());
+                const mtb_status s = mtb_builder_add_index(bld, old);
+                const std::string err = s == MTB_OK ? std::string() : std::string(mtb_last_error());
+                const unsigned long long n_old = mtb_index_num_targets(old);
+                mtb_index_close(old);
+                if (s != MTB_OK) die("add " + db + ": " + err);
+                fprintf(stderr, "mtb_build: %llu entries of %s\n", n_old, db.c_str());
+            }
+            n_rec = mtb_builder_num_records(bld);
+            mtb_index *ix = nullptr;
+            chk(mtb_builder_finish(bld, &ix), "mtb_builder_finish");
+            chk(mtb_index_write(ix, outdb.c_str(), split_num), "mtb_index_write");
+            n_entries = mtb_index_num_targets(ix);
+            mtb_index_close(ix);
+        } else {
+            if (mtb_builder_num_records(bld)) spill();
+            std::vector<const char *> dirs;
+            for (const std::string &p : parts) dirs.push_back(p.c_str());
+            for (const std::string &db : add_db) { dirs.push_back(db.c_str()); fprintf(stderr, "mtb_build: %llu entries of %s\n", entries_of(db), db.c_str()); }
+            const mtb_status s = mtb_merge_databases(ctx, dirs.data(), (uint32_t)dirs.size(), taxdir.c_str(), &par, outdb.c_str(), split_num, max_given ? max_records : 0, &ms);
+            const std::string err = s == MTB_OK ? std::string() : std::string(mtb_last_error());
+            remove_tree(parts_dir);
+            if (s != MTB_OK) die("mtb_merge_databases: " + err);
+            n_entries = ms.n_entries;
+        }
         const std::string otax = outdb + "/taxonomy";
         mkdir(otax.c_str(), 0755);
         {
@@ -188,14 +255,18 @@ int main(int argc, char **argv) {
             closedir(d);
             for (const std::string &n : names) copy_file(taxdir + "/" + n, otax + "/" + n);
         }
-        if (cds_list.empty())
-            fprintf(stderr, "mtb_build: %llu sequences (%llu bases), %llu records -> %llu entries in %s (six-frame extraction, no gene prediction)\n",
-                    n_seqs, n_bases, n_rec, (unsigned long long)mtb_index_num_targets(ix), outdb.c_str());
+        char route[96] = "";
+        if (streamed) snprintf(route, sizeof(route), " in %zu parts, %llu ranges", parts.size(), (unsigned long long)ms.n_ranges);
+        if (genomes == "-")
+            fprintf(stderr, "mtb_build: %zu databases (%llu entries) -> %llu entries in %s, merged in %llu ranges\n", add_db.size(), n_old, n_entries, outdb.c_str(),
+                    (unsigned long long)ms.n_ranges);
+        else if (cds_list.empty())
+            fprintf(stderr, "mtb_build: %llu sequences (%llu bases), %llu records -> %llu entries in %s%s (six-frame extraction, no gene prediction)\n",
+                    n_seqs, n_bases, n_rec, n_entries, outdb.c_str(), route);
         else
-            fprintf(stderr, "mtb_build: %llu sequences (%llu bases), %llu records -> %llu entries in %s (CDS annotation: %llu sequences by blocks -- %llu CDS, "
+            fprintf(stderr, "mtb_build: %llu sequences (%llu bases), %llu records -> %llu entries in %s%s (CDS annotation: %llu sequences by blocks -- %llu CDS, "
                             "%llu joined CDS, %llu non-CDS regions --, %llu sequences without a CDS entry in six frames; no gene prediction, no masking)\n",
-                    n_seqs, n_bases, n_rec, (unsigned long long)mtb_index_num_targets(ix), outdb.c_str(), n_by_blocks, n_cds_single, n_cds_joined, n_noncds, n_six_frames);
-        mtb_index_close(ix);
+                    n_seqs, n_bases, n_rec, n_entries, outdb.c_str(), route, n_by_blocks, n_cds_single, n_cds_joined, n_noncds, n_six_frames);
         mtb_builder_destroy(bld);
         mtb_ctx_destroy(ctx);
         return 0;

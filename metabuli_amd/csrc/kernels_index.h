@@ -61,22 +61,23 @@ __global__ void k_diff_add_carry(uint64_t *__restrict__ first_delta, const uint6
 __global__ void k_save_last(const uint64_t *__restrict__ last, uint64_t *__restrict__ carry) { *carry = *last; }
 
 /* ---------------- diffIdx encode (mtb_index_write): IndexCreator::getDiffIdx (IndexCreator.cpp:874-892) on the device ----------------
- * words of entry i = 15-bit groups of (value[i] - value[i-1]), most significant first, the last one flagged 0x8000 */
+ * words of entry i = 15-bit groups of (value[i] - value[i-1]), most significant first, the last one flagged 0x8000; entry 0 of the array is
+ * coded against prev0: 0 at the head of a database, the last value written before it when a database is written range by range */
 __device__ __forceinline__ uint32_t mtb_diff_words(uint64_t dlt) {
     const uint32_t bits = dlt ? 64u - (uint32_t)__clzll((unsigned long long)dlt) : 1u;
     return (bits + 14u) / 15u;
 }
-__global__ __launch_bounds__(256) void k_diff_nwords(const uint64_t *__restrict__ values, uint64_t i0, uint64_t m, uint32_t *__restrict__ nw) {
+__global__ __launch_bounds__(256) void k_diff_nwords(const uint64_t *__restrict__ values, uint64_t i0, uint64_t m, uint64_t prev0, uint32_t *__restrict__ nw) {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
     const uint64_t i = i0 + j;
-    nw[j] = mtb_diff_words(values[i] - (i ? values[i - 1] : 0ull));
+    nw[j] = mtb_diff_words(values[i] - (i ? values[i - 1] : prev0));
 }
-__global__ __launch_bounds__(256) void k_diff_encode(const uint64_t *__restrict__ values, uint64_t i0, uint64_t m, const uint64_t *__restrict__ off, uint16_t *__restrict__ enc) {
+__global__ __launch_bounds__(256) void k_diff_encode(const uint64_t *__restrict__ values, uint64_t i0, uint64_t m, uint64_t prev0, const uint64_t *__restrict__ off, uint16_t *__restrict__ enc) {
     const uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (j >= m) return;
     const uint64_t i = i0 + j;
-    const uint64_t dlt = values[i] - (i ? values[i - 1] : 0ull);
+    const uint64_t dlt = values[i] - (i ? values[i - 1] : prev0);
     const uint32_t n = mtb_diff_words(dlt);
     uint16_t *o = enc + off[j];
     for (uint32_t q = 0; q < n; q++) {

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <atomic>
@@ -18,11 +19,13 @@
 
 #include "../../include/mtb.h"
 #include "host_db.h"
+#include "host/merge_plan.h"
 #include "kernels_extract.h"
 #include "kernels_extract_blocks.h"
 #include "kernels_index.h"
 #include "kernels_join.h"
 #include "kernels_build.h"
+#include "kernels_merge.h"
 #include "kernels_dir.h"
 #include "kernels_scan.h"
 #include "kernels_score.h"
@@ -1898,130 +1901,207 @@ mtb_status mtb_index_download(mtb_index *ix, uint64_t *values, uint32_t *info, u
     if (info) HIPCHK(hipMemcpy(info, ix->d_info, ix->T * 4, hipMemcpyDeviceToHost));
     return MTB_OK;
 }
-/* IndexCreator::writeTargetFilesAndSplits + writeDbParameters (IndexCreator.cpp:817-892, 1251-1272) and the
- * taxID_list dump (:329-333) for an index that is resident on the device -- e.g. a synthetic one.  The delta coder runs on the
- * device, a slice of targets at a time (words per entry -> exclusive scan -> every entry writes its 15-bit groups at its offset), the
- * coded slice and its info entries cross PCIe into pinned buffers and a writer thread appends them to the files while the next slice
- * is coded; the split checkpoints -- armed at every size_of_split-th entry, recorded at the first later entry of another amino-acid
- * part -- are located by one small kernel up front and get their word offsets from the slice that holds them. */
+} // extern "C"
+
+/* IndexCreator::writeTargetFilesAndSplits + writeDbParameters (IndexCreator.cpp:817-892, 1251-1272) and the taxID_list dump (:329-333)
+ * for entries that are resident on the device -- all at once (mtb_index_write) or one value range after another (mtb_merge_databases:
+ * mergeTargetFiles<DB_CREATION>, IndexCreator.h:323-472, streams its output the same way).  append(): the delta coder runs on the
+ * device, a slice of targets at a time (words per entry -> exclusive scan -> every entry writes its 15-bit groups at its offset; the
+ * first entry of an append is coded against the last value written before it), the coded slice and its info entries cross PCIe into
+ * pinned buffers and a writer thread appends them to the files while the next slice is coded; the taxID_list map accumulates.
+ * finish(): the split checkpoints -- armed at every size_of_split-th entry, recorded at the first later entry of another amino-acid
+ * part -- need n, which only the end knows: every slice left a restart record {entry, word offset, previous value}, and the slices
+ * that hold an arming are looked at again -- in the caller's array if it is still resident, else re-decoded from the diffIdx just
+ * written, from exactly that record (decode_chunked).  An arming still pending at a slice's end is resolved in the next slice.
+ * db.parameters is removed first and written last: a directory whose write failed cannot be opened as a database. */
+struct IndexWriter {
+    struct Split { uint64_t ad, diff_off, info_off; };
+    struct Restart { uint64_t entry, word, prev, m, words; };        /* a slice: first entry, first word, the value before it, entries, words */
+    mtb_ctx *c = nullptr; std::string d; int fd = -1, fi = -1; int32_t max_id = 0; mtb_params params;
+    uint64_t SLICE = 0, n = 0, diff_count = 0, last_value = 0;
+    std::vector<Restart> restarts;
+    const uint64_t *resident = nullptr;          /* the one appended array, if it stays on the device until finish() (mtb_index_write) */
+    uint32_t *d_nw = nullptr; uint64_t *d_off = nullptr; uint16_t *d_enc = nullptr; uint8_t *d_seen = nullptr; int32_t *d_extra = nullptr; uint32_t *d_nextra = nullptr;
+    void *pin_e[2] = {nullptr, nullptr}, *pin_i[2] = {nullptr, nullptr};
+    std::thread writers[2]; std::atomic<bool> write_ok{true}; int cur = 0; bool begun = false;
+    static constexpr uint32_t EXTRA_CAP = 1u << 20;
+    void join() { for (int k = 0; k < 2; k++) if (writers[k].joinable()) writers[k].join(); }
+    ~IndexWriter() {
+        join();
+        if (fd >= 0) close(fd);
+        if (fi >= 0) close(fi);
+        for (int k = 0; k < 2; k++) { if (pin_e[k]) { hipError_t x = hipHostFree(pin_e[k]); (void)x; } if (pin_i[k]) { hipError_t x = hipHostFree(pin_i[k]); (void)x; } }
+        if (begun) { release(c, "wnw"); release(c, "woff"); release(c, "wenc"); release(c, "wseen"); release(c, "wextra"); }
+    }
+    /* slice_entries: the most entries one append will bring, if that is fewer than a slice of 2^25 (sizes the buffers of small databases) */
+    mtb_status begin(mtb_ctx *ctx, const char *dbdir, int32_t tax_max_id, const mtb_params &p, uint64_t slice_entries) {
+        c = ctx; d = dbdir; max_id = tax_max_id; params = p;
+        unlink((d + "/db.parameters").c_str());
+        fd = open((d + "/diffIdx").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644); fi = open((d + "/info").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+        if (fd < 0 || fi < 0) return fail(MTB_ERR_IO, "cannot create diffIdx/info in " + d);
+        SLICE = std::min<uint64_t>(1ull << 25, std::max<uint64_t>(slice_entries, 1));
+        begun = true;
+        STCHK(ensure(c, "wnw", SLICE, &d_nw)); STCHK(ensure(c, "woff", SLICE + 1, &d_off));
+        STCHK(ensure(c, "wenc", SLICE * 5, &d_enc)); STCHK(ensure(c, "wseen", (size_t)max_id + 2, &d_seen));
+        STCHK(ensure(c, "wextra", EXTRA_CAP + 1, &d_extra)); d_nextra = (uint32_t *)(d_extra + EXTRA_CAP);
+        HIPCHK(hipMemsetAsync(d_seen, 0, (size_t)max_id + 2, c->stream)); HIPCHK(hipMemsetAsync(d_nextra, 0, 4, c->stream));
+        for (int k = 0; k < 2; k++)
+            if (hipHostMalloc(&pin_e[k], SLICE * 10, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&pin_i[k], SLICE * 4, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError(); return fail(MTB_ERR_OOM, "no pinned host memory for the index download"); }
+        return MTB_OK;
+    }
+    /* m entries (device arrays), all above what was appended before */
+    mtb_status append(const uint64_t *d_values, const uint32_t *d_info, uint64_t m) {
+        hipStream_t st = c->stream;
+        const uint64_t prev0 = last_value;
+        uint64_t slice_prev = prev0;
+        for (uint64_t s0 = 0; s0 < m; s0 += SLICE, cur ^= 1) {
+            const uint64_t mm = std::min<uint64_t>(SLICE, m - s0);
+            const dim3 grid((uint32_t)((mm + 255) / 256));
+            uint64_t *d_ws;
+            STCHK(ensure(c, "scanws", scan_ws_elems(SLICE + 1), &d_ws));
+            hipLaunchKernelGGL(k_diff_nwords, grid, dim3(256), 0, st, d_values, s0, mm, prev0, d_nw);
+            scan_launch<uint32_t, uint64_t, false>(st, d_nw, mm, true, d_off, d_ws);
+            hipLaunchKernelGGL(k_diff_encode, grid, dim3(256), 0, st, d_values, s0, mm, prev0, (const uint64_t *)d_off, d_enc);
+            hipLaunchKernelGGL(k_mark_taxids, grid, dim3(256), 0, st, d_info, s0, mm, d_seen, max_id, d_extra, EXTRA_CAP, d_nextra);
+            HIPCHK(hipGetLastError());
+            uint64_t words = 0, slice_last = 0;
+            STCHK(d2h(c, &words, d_off + mm, 8));
+            STCHK(d2h(c, &slice_last, d_values + s0 + mm - 1, 8));
+            restarts.push_back(Restart{n + s0, diff_count, slice_prev, mm, words});
+            slice_prev = slice_last;
+            if (writers[cur].joinable()) writers[cur].join();  /* (two slices back: its buffers are `cur`'s) */
+            if (!write_ok) return fail(MTB_ERR_IO, "short write while writing " + d);
+            HIPCHK(hipMemcpyAsync(pin_e[cur], d_enc, words * 2, hipMemcpyDeviceToHost, st));          /* while the previous slice is being written from the other pair */
+            HIPCHK(hipMemcpyAsync(pin_i[cur], d_info + s0, mm * 4, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            if (writers[cur ^ 1].joinable()) writers[cur ^ 1].join();          /* file order */
+            if (!write_ok) return fail(MTB_ERR_IO, "short write while writing " + d);
+            const void *pe = pin_e[cur], *pi = pin_i[cur];
+            const uint64_t at_d = diff_count * 2, at_i = (n + s0) * 4;
+            std::atomic<bool> *ok = &write_ok; const int wfd = fd, wfi = fi;
+            /* several pwrite streams per file: one stream into the page cache tops out near 2-3 GB/s, a 16 G-target database is 150 GB */
+            writers[cur] = std::thread([ok, wfd, wfi, pe, pi, words, mm, at_d, at_i] {
+                bool ok_i = true;
+                std::thread ti([&] { ok_i = pwrite_parallel(wfi, pi, at_i, mm * 4, 6); });
+                const bool ok_d = pwrite_parallel(wfd, pe, at_d, words * 2, 10);
+                ti.join();
+                if (!ok_d || !ok_i) *ok = false;
+            });
+            diff_count += words;
+        }
+        n += m; last_value = slice_prev;
+        return MTB_OK;
+    }
+    /* the checkpoints: j[k] for every arming position k * size_of_split - 1; equal neighbours are one checkpoint (an arming inside a
+     * run that is still armed changes nothing); at most split_num - 1 are kept */
+    mtb_status find_splits(int split_num, std::vector<Split> *splits) {
+        hipStream_t st = c->stream;
+        const uint64_t size_of_split = n / (uint64_t)(split_num - 1);
+        if (!size_of_split || !n) return MTB_OK;
+        const uint64_t n_k = std::min<uint64_t>(n / size_of_split, 1u << 24);
+        size_t n_cp = 0; uint64_t last_j = UINT64_MAX; bool pending = false;
+        std::vector<uint64_t> armed, hj, cpj, cpv, cpo;
+        struct Scratch { mtb_ctx *c; ~Scratch() { release(c, "wdecv"); release(c, "wdeci"); release(c, "wsplitj"); release(c, "wcp"); release(c, "diffraw"); release(c, "difftc"); release(c, "difftoff"); } } scratch{c};
+        for (size_t r = 0; r < restarts.size() && n_cp + 1 < (size_t)split_num; r++) {
+            const Restart &R = restarts[r];
+            const uint64_t e = R.entry, end = R.entry + R.m;
+            armed.clear();
+            if (pending) armed.push_back(e - 1);                    /* still armed at the previous slice's last entry: every entry since the arming shares its amino-acid part */
+            pending = false;
+            const uint64_t k_lo = std::max<uint64_t>(1, (e + 1 + size_of_split - 1) / size_of_split), k_hi = std::min<uint64_t>(n_k, end / size_of_split);
+            for (uint64_t k = k_lo; k <= k_hi; k++) armed.push_back(k * size_of_split - 1);
+            if (armed.empty()) continue;
+            const uint64_t lead = e ? 1 : 0;
+            const uint64_t *vg = resident;                            /* indexed by the entry's number in the whole output */
+            if (!vg) {
+                uint64_t *dv; uint32_t *di;
+                STCHK(ensure(c, "wdecv", R.m + 2, &dv)); STCHK(ensure(c, "wdeci", R.m + 2, &di));
+                mtb_index tmp; tmp.ctx = c; tmp.params = params; tmp.d_values = dv; tmp.d_info = di;
+                OpenPlan P; P.n16 = R.words; P.T = R.m + lead; P.expect = R.m; P.lead = lead; P.diff_off = R.word; P.info_off = e - lead; P.first_value = R.prev;
+                bool dir_ok = false;
+                STCHK(decode_chunked(c, &tmp, d, P, false, 1, false, &dir_ok));
+                vg = dv - (e - lead);
+            }
+            const uint32_t na = (uint32_t)armed.size();
+            uint64_t *d_j, *d_ws, *d_cp;
+            STCHK(ensure(c, "wsplitj", 2 * (size_t)na, &d_j));
+            STCHK(h2d(c, d_j, armed.data(), (size_t)na * 8));
+            hipLaunchKernelGGL(k_split_find_win, dim3((na + 255) / 256), dim3(256), 0, st, vg, end, n, (const uint64_t *)d_j, na, d_j + na);
+            HIPCHK(hipGetLastError());
+            hj.resize(na);
+            STCHK(d2h(c, hj.data(), d_j + na, (size_t)na * 8));
+            cpj.clear();
+            for (uint32_t t = 0; t < na && n_cp + cpj.size() + 1 < (size_t)split_num; t++) {
+                if (hj[t] == UINT64_MAX) { pending = true; break; }
+                if (hj[t] < n && hj[t] != last_j) { cpj.push_back(hj[t]); last_j = hj[t]; }
+            }
+            if (cpj.empty()) continue;
+            /* value and word offset BEHIND each checkpoint's entry: the slice's words per entry, scanned again */
+            const uint32_t q = (uint32_t)cpj.size();
+            STCHK(ensure(c, "wcp", 3 * (size_t)q, &d_cp));
+            STCHK(ensure(c, "scanws", scan_ws_elems(SLICE + 1), &d_ws));
+            STCHK(h2d(c, d_cp, cpj.data(), (size_t)q * 8));
+            hipLaunchKernelGGL(k_diff_nwords, dim3((uint32_t)((R.m + 255) / 256)), dim3(256), 0, st, vg, e, R.m, R.prev, d_nw);
+            scan_launch<uint32_t, uint64_t, false>(st, d_nw, R.m, true, d_off, d_ws);
+            hipLaunchKernelGGL(k_split_gather, dim3((q + 63) / 64), dim3(64), 0, st, vg, (const uint64_t *)d_off, e, (const uint64_t *)d_cp, q, d_cp + q, d_cp + 2 * (size_t)q);
+            HIPCHK(hipGetLastError());
+            cpv.resize(q); cpo.resize(q);
+            STCHK(d2h(c, cpv.data(), d_cp + q, (size_t)q * 8)); STCHK(d2h(c, cpo.data(), d_cp + 2 * (size_t)q, (size_t)q * 8));
+            for (uint32_t t = 0; t < q; t++) (*splits)[++n_cp] = Split{cpv[t], R.word + cpo[t], cpj[t] + 1};
+        }
+        return MTB_OK;
+    }
+    mtb_status finish(int split_num) {
+        join();
+        if (!write_ok) return fail(MTB_ERR_IO, "short write while writing " + d);
+        std::vector<Split> splits((size_t)split_num, Split{0, 0, 0});
+        STCHK(find_splits(split_num, &splits));
+        std::vector<uint8_t> seen((size_t)max_id + 2, 0);
+        STCHK(d2h(c, seen.data(), d_seen, seen.size()));
+        uint32_t n_extra = 0;
+        STCHK(d2h(c, &n_extra, d_nextra, 4));
+        if (n_extra > EXTRA_CAP) return fail(MTB_ERR_UNSUPPORTED, "more than 2^20 info entries outside the taxonomy's id range");
+        std::vector<int32_t> extra_ids(n_extra);           /* ids outside the taxonomy's range (kept for taxID_list) */
+        if (n_extra) STCHK(d2h(c, extra_ids.data(), d_extra, (size_t)n_extra * 4));
+        FILE *f = fopen((d + "/split").c_str(), "wb"); if (!f) return fail(MTB_ERR_IO, "cannot create " + d + "/split");
+        fwrite(splits.data(), sizeof(Split), splits.size(), f); fclose(f);
+        std::sort(extra_ids.begin(), extra_ids.end()); extra_ids.erase(std::unique(extra_ids.begin(), extra_ids.end()), extra_ids.end());
+        f = fopen((d + "/taxID_list").c_str(), "w"); if (!f) return fail(MTB_ERR_IO, "cannot create " + d + "/taxID_list");
+        {   size_t e = 0;
+            for (size_t t = 0; t < seen.size(); t++) {
+                while (e < extra_ids.size() && extra_ids[e] < (int32_t)t) fprintf(f, "%d\n", extra_ids[e++]);
+                if (seen[t]) fprintf(f, "%zu\n", t);
+            }
+            while (e < extra_ids.size()) fprintf(f, "%d\n", extra_ids[e++]);
+        }
+        fclose(f);
+        if (close(fd) != 0 || close(fi) != 0) { fd = fi = -1; return fail(MTB_ERR_IO, "cannot close diffIdx/info in " + d); }
+        fd = fi = -1;
+        f = fopen((d + "/db.parameters").c_str(), "w"); if (!f) return fail(MTB_ERR_IO, "cannot create " + d + "/db.parameters");
+        const mtb_params &p = params;
+        fprintf(f, "DB_name\t%s\nCreation_date\t-\nReduced_alphabet\t0\nAccession_level\t%d\n", "mtb", p.accession_level == 2 ? 1 : 0);
+        fprintf(f, "Mask_mode\t0\nMask_prob\t0.900000\nSkip_redundancy\t%d\nSyncmer\t%d\n", p.skip_redundancy ? 1 : 0, p.syncmer);
+        if (p.syncmer == 1) fprintf(f, "Syncmer_len\t%d\n", p.smer_len);
+        fprintf(f, "Kmer_format\t%d\n", p.kmer_format);
+        fclose(f);
+        return MTB_OK;
+    }
+};
+
+extern "C" {
+
 mtb_status mtb_index_write(const mtb_index *cix, const char *dbdir, int split_num) {
     if (!cix || !dbdir || split_num < 2) return fail(MTB_ERR_ARG, "NULL argument / split_num < 2");
     mtb_index *ix = const_cast<mtb_index *>(cix);
     mtb_ctx *c = ix->ctx;
     HIPCHK(hipSetDevice(c->device));
     STCHK(ensure_flat(ix));
-    hipStream_t st = c->stream;
-    const std::string d(dbdir);
-    const int fd = open((d + "/diffIdx").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644), fi = open((d + "/info").c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    struct Files { int a, b; ~Files() { if (a >= 0) close(a); if (b >= 0) close(b); } } files{fd, fi};
-    if (fd < 0 || fi < 0) return fail(MTB_ERR_IO, "cannot create diffIdx/info in " + d);
-    struct Split { uint64_t ad, diff_off, info_off; };
-    std::vector<Split> splits((size_t)split_num, Split{0, 0, 0});
-    const uint64_t n = ix->T;
-    const uint64_t size_of_split = n / (uint64_t)(split_num - 1);
-    /* where the checkpoints fall: j[k] for every arming position k * size_of_split; equal neighbours are one checkpoint (an arming
-     * inside a run that is still armed changes nothing); at most split_num - 1 are kept */
-    std::vector<uint64_t> cps;
-    if (size_of_split && n) {
-        const uint64_t n_k64 = n / size_of_split;
-        const uint32_t n_k = (uint32_t)std::min<uint64_t>(n_k64, 1u << 24);
-        uint64_t *d_j;
-        STCHK(ensure(c, "wsplitj", n_k, &d_j));
-        hipLaunchKernelGGL(k_split_find, dim3((n_k + 255) / 256), dim3(256), 0, st, (const uint64_t *)ix->d_values, n, size_of_split, n_k, d_j);
-        HIPCHK(hipGetLastError());
-        std::vector<uint64_t> hj(n_k);
-        STCHK(d2h(c, hj.data(), d_j, (size_t)n_k * 8));
-        for (uint32_t k = 0; k < n_k && cps.size() + 1 < (size_t)split_num; k++) if (hj[k] < n && (cps.empty() || cps.back() != hj[k])) cps.push_back(hj[k]);
-        release(c, "wsplitj");
-    }
-    const uint64_t SLICE = std::min<uint64_t>(1ull << 25, std::max<uint64_t>(n, 1));
-    uint32_t *d_nw; uint64_t *d_off, *d_ws; uint16_t *d_enc; uint8_t *d_seen; int32_t *d_extra; uint32_t *d_nextra; uint64_t *d_cpj, *d_cpv, *d_cpo;
-    const uint32_t EXTRA_CAP = 1u << 20;
-    STCHK(ensure(c, "wnw", SLICE, &d_nw)); STCHK(ensure(c, "woff", SLICE + 1, &d_off)); STCHK(ensure(c, "scanws", scan_ws_elems(SLICE + 1), &d_ws));
-    STCHK(ensure(c, "wenc", SLICE * 5, &d_enc)); STCHK(ensure(c, "wseen", (size_t)ix->tax.max_id + 2, &d_seen));
-    STCHK(ensure(c, "wextra", EXTRA_CAP + 1, &d_extra)); d_nextra = (uint32_t *)(d_extra + EXTRA_CAP);
-    STCHK(ensure(c, "wcp", 3 * (cps.size() + 1), &d_cpj)); d_cpv = d_cpj + cps.size() + 1; d_cpo = d_cpv + cps.size() + 1;
-    HIPCHK(hipMemsetAsync(d_seen, 0, (size_t)ix->tax.max_id + 2, st)); HIPCHK(hipMemsetAsync(d_nextra, 0, 4, st));
-    if (!cps.empty()) STCHK(h2d(c, d_cpj, cps.data(), cps.size() * 8));
-    struct Pinned { void *e[2] = {nullptr, nullptr}, *i[2] = {nullptr, nullptr}; ~Pinned() { for (int k = 0; k < 2; k++) { if (e[k]) { hipError_t x = hipHostFree(e[k]); (void)x; } if (i[k]) { hipError_t x = hipHostFree(i[k]); (void)x; } } } } pin;
-    for (int k = 0; k < 2; k++)
-        if (hipHostMalloc(&pin.e[k], SLICE * 10, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&pin.i[k], SLICE * 4, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError(); return fail(MTB_ERR_OOM, "no pinned host memory for the index download"); }
-    std::thread writers[2]; bool write_ok = true;         /* writers[k]: appends the slice that sits in buffer pair k; one at a time, in slice order */
-    struct Join { std::thread *t; ~Join() { for (int k = 0; k < 2; k++) if (t[k].joinable()) t[k].join(); } } join_writers{writers};
-    uint64_t diff_count = 0; size_t cp_at = 0; int cur = 0;
-    std::vector<uint64_t> cpv, cpo;
-    for (uint64_t s0 = 0; s0 < n; s0 += SLICE, cur ^= 1) {
-        const uint64_t m = std::min<uint64_t>(SLICE, n - s0);
-        const dim3 grid((uint32_t)((m + 255) / 256));
-        hipLaunchKernelGGL(k_diff_nwords, grid, dim3(256), 0, st, (const uint64_t *)ix->d_values, s0, m, d_nw);
-        scan_launch<uint32_t, uint64_t, false>(st, d_nw, m, true, d_off, d_ws);
-        hipLaunchKernelGGL(k_diff_encode, grid, dim3(256), 0, st, (const uint64_t *)ix->d_values, s0, m, (const uint64_t *)d_off, d_enc);
-        hipLaunchKernelGGL(k_mark_taxids, grid, dim3(256), 0, st, (const uint32_t *)ix->d_info, s0, m, d_seen, ix->tax.max_id, d_extra, EXTRA_CAP, d_nextra);
-        HIPCHK(hipGetLastError());
-        uint64_t words = 0;
-        STCHK(d2h(c, &words, d_off + m, 8));
-        /* checkpoints inside this slice: value and word offset behind the entry */
-        size_t cp_hi = cp_at;
-        while (cp_hi < cps.size() && cps[cp_hi] < s0 + m) cp_hi++;
-        if (cp_hi > cp_at) {
-            const uint32_t q = (uint32_t)(cp_hi - cp_at);
-            hipLaunchKernelGGL(k_split_gather, dim3((q + 63) / 64), dim3(64), 0, st, (const uint64_t *)ix->d_values, (const uint64_t *)d_off, s0, (const uint64_t *)(d_cpj + cp_at), q, d_cpv, d_cpo);
-            HIPCHK(hipGetLastError());
-            cpv.resize(q); cpo.resize(q);
-            STCHK(d2h(c, cpv.data(), d_cpv, (size_t)q * 8)); STCHK(d2h(c, cpo.data(), d_cpo, (size_t)q * 8));
-            for (uint32_t t = 0; t < q; t++) splits[cp_at + t + 1] = Split{cpv[t], diff_count + cpo[t], cps[cp_at + t] + 1};
-            cp_at = cp_hi;
-        }
-        if (writers[cur].joinable()) writers[cur].join();  /* (two slices back: its buffers are `cur`'s) */
-        if (!write_ok) return fail(MTB_ERR_IO, "short write while writing " + d);
-        HIPCHK(hipMemcpyAsync(pin.e[cur], d_enc, words * 2, hipMemcpyDeviceToHost, st));          /* while the previous slice is being written from the other pair */
-        HIPCHK(hipMemcpyAsync(pin.i[cur], ix->d_info + s0, m * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (writers[cur ^ 1].joinable()) writers[cur ^ 1].join();          /* file order */
-        if (!write_ok) return fail(MTB_ERR_IO, "short write while writing " + d);
-        const void *pe = pin.e[cur], *pi = pin.i[cur];
-        const uint64_t at_d = diff_count * 2, at_i = s0 * 4;
-        /* several pwrite streams per file: one stream into the page cache tops out near 2-3 GB/s, a 16 G-target database is 150 GB */
-        writers[cur] = std::thread([&write_ok, fd, fi, pe, pi, words, m, at_d, at_i] {
-            bool ok_i = true;
-            std::thread ti([&] { ok_i = pwrite_parallel(fi, pi, at_i, m * 4, 6); });
-            const bool ok_d = pwrite_parallel(fd, pe, at_d, words * 2, 10);
-            ti.join();
-            if (!ok_d || !ok_i) write_ok = false;
-        });
-        diff_count += words;
-    }
-    for (int k = 0; k < 2; k++) if (writers[k].joinable()) writers[k].join();
-    if (!write_ok) return fail(MTB_ERR_IO, "short write while writing " + d);
-    std::vector<uint8_t> seen((size_t)ix->tax.max_id + 2, 0);
-    STCHK(d2h(c, seen.data(), d_seen, seen.size()));
-    uint32_t n_extra = 0;
-    STCHK(d2h(c, &n_extra, d_nextra, 4));
-    if (n_extra > EXTRA_CAP) return fail(MTB_ERR_UNSUPPORTED, "more than 2^20 info entries outside the taxonomy's id range");
-    std::vector<int32_t> extra_ids(n_extra);           /* ids outside the taxonomy's range (kept for taxID_list) */
-    if (n_extra) STCHK(d2h(c, extra_ids.data(), d_extra, (size_t)n_extra * 4));
-    release(c, "wnw"); release(c, "woff"); release(c, "wenc"); release(c, "wseen"); release(c, "wextra"); release(c, "wcp");
-    FILE *f = fopen((d + "/split").c_str(), "wb"); if (!f) return fail(MTB_ERR_IO, "cannot create " + d + "/split");
-    fwrite(splits.data(), sizeof(Split), splits.size(), f); fclose(f);
-    std::sort(extra_ids.begin(), extra_ids.end()); extra_ids.erase(std::unique(extra_ids.begin(), extra_ids.end()), extra_ids.end());
-    f = fopen((d + "/taxID_list").c_str(), "w"); if (!f) return fail(MTB_ERR_IO, "cannot create " + d + "/taxID_list");
-    {   size_t e = 0;
-        for (size_t t = 0; t < seen.size(); t++) {
-            while (e < extra_ids.size() && extra_ids[e] < (int32_t)t) fprintf(f, "%d\n", extra_ids[e++]);
-            if (seen[t]) fprintf(f, "%zu\n", t);
-        }
-        while (e < extra_ids.size()) fprintf(f, "%d\n", extra_ids[e++]);
-    }
-    fclose(f);
-    f = fopen((d + "/db.parameters").c_str(), "w"); if (!f) return fail(MTB_ERR_IO, "cannot create " + d + "/db.parameters");
-    const mtb_params &p = ix->params;
-    fprintf(f, "DB_name\t%s\nCreation_date\t-\nReduced_alphabet\t0\nAccession_level\t%d\n", "mtb", p.accession_level == 2 ? 1 : 0);
-    fprintf(f, "Mask_mode\t0\nMask_prob\t0.900000\nSkip_redundancy\t%d\nSyncmer\t%d\n", p.skip_redundancy ? 1 : 0, p.syncmer);
-    if (p.syncmer == 1) fprintf(f, "Syncmer_len\t%d\n", p.smer_len);
-    fprintf(f, "Kmer_format\t%d\n", p.kmer_format);
-    fclose(f);
-    return MTB_OK;
+    IndexWriter w;
+    STCHK(w.begin(c, dbdir, ix->tax.max_id, ix->params, ix->T));
+    STCHK(w.append(ix->d_values, ix->d_info, ix->T));
+    w.resident = ix->d_values;
+    return w.finish(split_num);
 }
 
 int32_t mtb_tax_lca(const mtb_index *ix, int32_t a, int32_t b) { return ix->tax.lca(a, b); }
@@ -3715,6 +3795,16 @@ void mtb_builder_destroy(mtb_builder *b) {
 
 uint64_t mtb_builder_num_records(const mtb_builder *b) { return b ? b->n : 0; }
 
+mtb_status mtb_builder_capacity(const mtb_builder *b, uint64_t *max_records) {
+    if (!b || !max_records) return fail(MTB_ERR_ARG, "NULL argument");
+    HIPCHK(hipSetDevice(b->ctx->device));
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    const uint64_t avail = (uint64_t)fr + b->cap * sizeof(mtb_kmer) + held_bytes(b->ctx, BUF_FIXED);
+    *max_records = std::min<uint64_t>(avail / 72, 0xFFFFFFFFull);
+    return MTB_OK;
+}
+
 mtb_status mtb_builder_add_records(mtb_builder *b, const uint64_t *values, const int32_t *taxids, uint64_t n) {
     if (!b || (n && (!values || !taxids))) return fail(MTB_ERR_ARG, "NULL argument");
     if (n == 0) return MTB_OK;
@@ -3821,7 +3911,7 @@ mtb_status mtb_builder_finish(mtb_builder *b, mtb_index **out) {
     *out = nullptr;
     const uint64_t n = b->n;
     if (n == 0) return fail(MTB_ERR_ARG, "the builder holds no records");
-    if (n >= (1ull << 32)) return fail(MTB_ERR_ARG, "2^32 or more records in one finish (" + std::to_string(n) + "): the device sort takes fewer than 2^32; build in parts and merge them with mtb_builder_add_index");
+    if (n >= (1ull << 32)) return fail(MTB_ERR_ARG, "2^32 or more records in one finish (" + std::to_string(n) + "): the device sort takes fewer than 2^32; build in parts (mtb_build --max-records) and merge the written parts with mtb_merge_databases");
     mtb_ctx *c = b->ctx;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -3905,6 +3995,236 @@ mtb_status mtb_builder_last_finish_stats(const mtb_builder *b, mtb_build_stats *
     if (!b || !out) return fail(MTB_ERR_ARG, "NULL argument");
     for (int k = 0; k < MTB_BUILD_STAGES; k++) out->ms[k] = b->ms[k];
     out->n_records = b->last_n; out->n_entries = b->last_groups; out->n_long_groups = b->last_long;
+    return MTB_OK;
+}
+
+} // extern "C"
+
+
+/* ------------------------------------------------------------------ */
+/* streamed merge of databases (kernels_merge.h, host/merge_plan.h)    */
+/* ------------------------------------------------------------------ */
+/* out[0, na + nb) = the merge of the sorted lists a and b (device pointers; out overlaps neither) */
+static mtb_status dev_merge2(mtb_ctx *c, const mtb_kmer *a, uint64_t na, const mtb_kmer *b, uint64_t nb, mtb_kmer *out) {
+    if (na == 0 || nb == 0) {
+        if (na + nb) HIPCHK(hipMemcpyAsync(out, na ? a : b, (na + nb) * sizeof(mtb_kmer), hipMemcpyDeviceToDevice, c->stream));
+        return MTB_OK;
+    }
+    const uint64_t total = na + nb, n_tiles = (total + MTB_MERGE_TILE - 1) / MTB_MERGE_TILE;
+    uint64_t *d_split;
+    STCHK(ensure(c, "mrgsplit", n_tiles + 1, &d_split));
+    hipLaunchKernelGGL(k_merge_partition, dim3((uint32_t)((n_tiles + 1 + 255) / 256)), dim3(256), 0, c->stream, a, na, b, nb, n_tiles, d_split);
+    hipLaunchKernelGGL(k_merge_tile, dim3((uint32_t)n_tiles), dim3(MTB_MERGE_THREADS), 0, c->stream, a, b, total, (const uint64_t *)d_split, out);
+    HIPCHK(hipGetLastError());
+    return MTB_OK;
+}
+
+/* k sorted lists that lie back to back in `ping` (list i = records [off[i], off[i + 1])) -> one sorted list: a pairwise tree between
+ * the two buffers, an odd list of a level is copied.  *result = the buffer that holds it. */
+static mtb_status dev_merge_tree(mtb_ctx *c, mtb_kmer *ping, mtb_kmer *pong, std::vector<uint64_t> off, mtb_kmer **result) {
+    mtb_kmer *src = ping, *dst = pong;
+    while (off.size() > 2) {
+        std::vector<uint64_t> next;
+        for (size_t i = 0; i + 1 < off.size(); i += 2) {
+            next.push_back(off[i]);
+            const uint64_t na = off[i + 1] - off[i], nb = i + 2 < off.size() ? off[i + 2] - off[i + 1] : 0;
+            STCHK(dev_merge2(c, src + off[i], na, src + off[i + 1], nb, dst + off[i]));
+        }
+        next.push_back(off.back());
+        off.swap(next);
+        std::swap(src, dst);
+    }
+    *result = src;
+    return MTB_OK;
+}
+
+namespace {
+struct MergeSource { std::string dir; uint32_t info_mask = 0xFFFFFFFFu; mtbhost::MergeInput plan; };
+double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+}
+
+extern "C" {
+
+mtb_status mtb_merge_sorted(mtb_ctx *c, const mtb_kmer *a, uint64_t n_a, const mtb_kmer *b, uint64_t n_b, mtb_kmer *out) {
+    if (!c || (n_a && !a) || (n_b && !b) || ((n_a + n_b) && !out)) return fail(MTB_ERR_ARG, "NULL argument");
+    if (n_a + n_b == 0) return MTB_OK;
+    HIPCHK(hipSetDevice(c->device));
+    mtb_kmer *d_in, *d_out;
+    STCHK(ensure(c, "mrgA", n_a + n_b, &d_in)); STCHK(ensure(c, "mrgB", n_a + n_b, &d_out));
+    if (n_a) STCHK(h2d(c, d_in, a, n_a * sizeof(mtb_kmer)));
+    if (n_b) STCHK(h2d(c, d_in + n_a, b, n_b * sizeof(mtb_kmer)));
+    STCHK(dev_merge2(c, d_in, n_a, d_in + n_a, n_b, d_out));
+    STCHK(d2h(c, out, d_out, (n_a + n_b) * sizeof(mtb_kmer)));
+    return MTB_OK;
+}
+
+mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n_dbs, const char *taxonomy_dir, const mtb_params *params,
+                               const char *outdir, int split_num, uint64_t max_range_records, mtb_merge_stats *stats) {
+    if (!c || !taxonomy_dir || !params || !outdir || split_num < 2) return fail(MTB_ERR_ARG, "NULL argument / split_num < 2");
+    unlink((std::string(outdir) + "/db.parameters").c_str());          /* whatever happens below: no half-written database that opens */
+    if (n_dbs == 0 || !dbdirs) return fail(MTB_ERR_ARG, "no databases to merge");
+    if (params->kmer_format != 1 && params->kmer_format != 2) return fail(MTB_ERR_UNSUPPORTED, "only kmer_format 1 and 2 are implemented");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const auto t_all = std::chrono::steady_clock::now();
+    mtb_merge_stats S; memset(&S, 0, sizeof(S));
+    /* the inputs: parameters, checkpoints, sizes */
+    std::vector<MergeSource> src(n_dbs);
+    std::vector<mtbhost::MergeInput> inputs(n_dbs);
+    for (uint32_t i = 0; i < n_dbs; i++) {
+        if (!dbdirs[i]) return fail(MTB_ERR_ARG, "NULL database directory");
+        MergeSource &s = src[i]; s.dir = dbdirs[i];
+        /* what the database says of itself: the keys that db.parameters can only switch ON start switched off */
+        mtb_params q = *params; q.syncmer = 0; int reduced_aa = 0;
+        const bool have_par = mtbhost::file_exists(s.dir + "/db.parameters");
+        if (have_par) q.skip_redundancy = 0;
+        mtbhost::load_db_parameters(s.dir, &q, &reduced_aa);
+        if (!have_par) q.syncmer = params->syncmer;
+        if (reduced_aa) return fail(MTB_ERR_UNSUPPORTED, "database " + s.dir + " was built with the reduced amino-acid alphabet (Reduced_alphabet 1 in db.parameters); not implemented");
+        if (q.kmer_format != params->kmer_format || (q.syncmer != 0) != (params->syncmer != 0) || (params->syncmer && q.smer_len != params->smer_len))
+            return fail(MTB_ERR_ARG, "kmer_format / syncmer / smer_len of " + s.dir + " differ from the merge's parameters");
+        s.info_mask = ~((uint32_t)(q.skip_redundancy == 0) << 31);       /* legacy databases: bit 31 is a flag (IndexCreator.h:355, 400) */
+        struct stat sd, si;
+        if (stat((s.dir + "/diffIdx").c_str(), &sd) != 0 || stat((s.dir + "/info").c_str(), &si) != 0) return fail(MTB_ERR_IO, "cannot open diffIdx / info in " + s.dir);
+        std::vector<mtbhost::MergeCheckpoint> sp;
+        if (mtbhost::file_exists(s.dir + "/split") && !mtbhost::read_whole(s.dir + "/split", &sp)) return fail(MTB_ERR_IO, "cannot read " + s.dir + "/split");
+        mtbhost::merge_input_from_split(sp.data(), sp.size(), (uint64_t)si.st_size / 4, (uint64_t)sd.st_size / 2, &inputs[i]);
+        S.n_input_entries += inputs[i].n_entries;
+    }
+    /* the taxonomy of the merge, on the device: a holder index without targets.  The species table covers every node: for an id that
+     * occurs it holds what the table built from the ids that occur (mtb_builder_finish) holds. */
+    mtb_index *hold = new mtb_index();
+    struct Guard { mtb_index *ix; ~Guard() { mtb_index_close(ix); } } guard{hold};
+    hold->ctx = c; hold->params = *params; hold->params.skip_redundancy = 1; hold->own = true;
+    {   std::string err;
+        mtb_params q = *params; int reduced_aa = 0;
+        mtbhost::load_db_parameters(std::string(taxonomy_dir) + "/..", &q, &reduced_aa);
+        if (reduced_aa) return fail(MTB_ERR_UNSUPPORTED, "Reduced_alphabet 1 is not implemented");
+        if (!mtbhost::load_taxonomy(taxonomy_dir, &hold->tax, &err)) return fail(MTB_ERR_IO, err);
+        std::vector<int32_t> ids;
+        for (int32_t t = 0; t <= hold->tax.max_id; t++) if (hold->tax.cn(t) >= 0) ids.push_back(t);
+        mtbhost::build_tax2species(&hold->tax, ids.data(), ids.size()); }
+    STCHK(upload_taxonomy(hold));
+    const mtb_tax_view tv = tax_view(hold);
+    const int bits = mtb_build_tax_bits(hold->tax.max_id);
+    /* the ranges */
+    uint64_t budget = max_range_records;
+    if (budget == 0) {
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        fr += held_bytes(c, BUF_WORK);
+        const uint64_t fixed = 4ull << 30;                             /* decode chunks, the writer's slice buffers, scan workspace */
+        budget = fr > 2 * fixed ? (fr - fixed) / MTB_MERGE_BYTES_PER_RECORD : std::max<uint64_t>(fr / (2 * MTB_MERGE_BYTES_PER_RECORD), 1);
+    }
+    budget = std::min<uint64_t>(budget, 0xFFFFFFFFull);
+    std::vector<mtbhost::MergeRange> ranges;
+    {   uint64_t needed = 0;
+        if (mtbhost::merge_plan(inputs, budget, &ranges, &needed) != mtbhost::MERGE_PLAN_OK)
+            return fail(MTB_ERR_CAPACITY, "one checkpoint interval of the inputs holds " + std::to_string(needed) + " records, more than max_range_records = " + std::to_string(budget) +
+                                          ": the merge needs room for " + std::to_string(needed) + " records"); }
+    uint64_t max_rec = 0;
+    for (const mtbhost::MergeRange &r : ranges) max_rec = std::max(max_rec, r.records);
+    S.n_ranges = ranges.size(); S.max_range_records_used = max_rec;
+    IndexWriter w;
+    STCHK(w.begin(c, outdir, hold->tax.max_id, hold->params, max_rec));
+    struct Scratch { mtb_ctx *c; ~Scratch() { for (const char *nm : {"mrgA", "mrgB", "mrgsplit", "mrgov", "mrgoi", "bhead", "bpos", "blist", "diffraw", "difftc", "difftoff", "kmersB", "hist"}) release(c, nm); } } scratch{c};
+    unsigned long long *d_bad = scal<unsigned long long>(c, SC_JOIN_COUNT);
+    uint32_t *d_unsorted = scal<uint32_t>(c, SC_JOIN_OVERFLOW);
+    uint64_t *d_trim = scal<uint64_t>(c, SC_N_LARGE);                  /* two words: SC_N_LARGE, SC_MAX_SEG */
+    for (const mtbhost::MergeRange &R : ranges) {
+        if (R.records == 0) continue;
+        mtb_kmer *d_a, *d_b;
+        STCHK(ensure(c, "mrgA", R.records + 1, &d_a)); STCHK(ensure(c, "mrgB", R.records + 1, &d_b));
+        std::vector<uint64_t> off(1, 0);
+        auto t0 = std::chrono::steady_clock::now();
+        for (uint32_t i = 0; i < n_dbs; i++) {
+            const mtbhost::MergeSlice &sl = R.slices[i];
+            const uint64_t T = sl.records();
+            if (T == 0) continue;
+            /* the slice is decoded into the buffer the merge has not written yet: T + 1 values, then T info entries */
+            uint64_t *dv = (uint64_t *)d_b; uint32_t *di = (uint32_t *)(dv + T + 1);
+            mtb_index tmp; tmp.ctx = c; tmp.params = *params; tmp.d_values = dv; tmp.d_info = di;
+            OpenPlan P; P.n16 = sl.diff_hi - sl.diff_lo; P.T = T; P.lead = sl.lead; P.expect = T - sl.lead + (sl.drop_last ? 1 : 0);
+            P.diff_off = sl.diff_lo; P.info_off = sl.info_lo; P.first_value = sl.first_value;
+            bool dir_ok = false;
+            STCHK(decode_chunked(c, &tmp, src[i].dir, P, false, 1, false, &dir_ok));
+            hipLaunchKernelGGL(k_merge_trim, dim3(1), dim3(64), 0, st, (const uint64_t *)dv, T, R.lo, R.hi, d_trim);
+            HIPCHK(hipGetLastError());
+            uint64_t ab[2] = {0, 0};
+            STCHK(d2h(c, ab, d_trim, 16));
+            const uint64_t cnt = ab[1] - ab[0];
+            if (cnt == 0) continue;
+            mtb_kmer *rec = d_a + off.back();
+            HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, st)); HIPCHK(hipMemsetAsync(d_unsorted, 0, 8, st));
+            hipLaunchKernelGGL(k_merge_keys, grid256(cnt), dim3(256), 0, st, (const uint64_t *)(dv + ab[0]), (const uint32_t *)(di + ab[0]), cnt, src[i].info_mask, tv,
+                               (const int32_t *)hold->d_tax2species, rec, d_bad, d_unsorted);
+            HIPCHK(hipGetLastError());
+            uint64_t flags[2] = {0, 0};
+            STCHK(d2h(c, flags, d_bad, 16));                            /* SC_JOIN_COUNT, SC_JOIN_OVERFLOW are adjacent */
+            if (flags[0] != ~0ull) {
+                mtb_kmer r;
+                STCHK(d2h(c, &r, rec + flags[0], sizeof(r)));
+                return fail(MTB_ERR_ARG, "taxid " + std::to_string(mtb_build_key_taxid(r.qinfo)) + " of " + src[i].dir + " (entry " + std::to_string(sl.info_lo + ab[0] + flags[0]) +
+                                         ") is not in the merge's taxonomy");
+            }
+            if ((uint32_t)flags[1]) {
+                /* built under another taxonomy: not ascending under this one -- the builder's two radix sorts, for this slice alone */
+                mtb_kmer *d_s;
+                hipLaunchKernelGGL(k_merge_sort_key, grid256(cnt), dim3(256), 0, st, rec, cnt, bits);
+                STCHK(dev_sort(c, rec, cnt, mtb_build_key_first_bit(bits), &d_s, nullptr, 0));
+                hipLaunchKernelGGL(k_build_swap, grid256(cnt), dim3(256), 0, st, (const mtb_kmer *)d_s, cnt, bits, rec);
+                STCHK(dev_sort(c, rec, cnt, 0, &d_s, nullptr, 0));
+                if (d_s != rec) HIPCHK(hipMemcpyAsync(rec, d_s, cnt * sizeof(mtb_kmer), hipMemcpyDeviceToDevice, st));
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(st));
+                S.n_resorted_slices++;
+            }
+            off.push_back(off.back() + cnt);
+        }
+        S.ms_read_decode += (float)ms_since(t0);
+        const uint64_t n = off.back();
+        if (n == 0) continue;
+        t0 = std::chrono::steady_clock::now();
+        mtb_kmer *d_s;
+        STCHK(dev_merge_tree(c, d_a, d_b, off, &d_s));
+        HIPCHK(hipStreamSynchronize(st));
+        S.ms_merge += (float)ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        uint32_t *d_head, *d_pos, *d_list; uint64_t *d_ws;
+        STCHK(ensure(c, "bhead", n, &d_head)); STCHK(ensure(c, "bpos", n + 1, &d_pos));
+        STCHK(ensure(c, "scanws", scan_ws_elems(n + 1), &d_ws));
+        hipLaunchKernelGGL(k_build_heads, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, d_head);
+        scan_launch<uint32_t, uint32_t, false>(st, d_head, n, true, d_pos, (uint32_t *)d_ws);
+        HIPCHK(hipGetLastError());
+        uint32_t n_groups = 0;
+        STCHK(d2h(c, &n_groups, d_pos + n, 4));
+        const uint64_t G = n_groups;
+        uint64_t *d_ov; uint32_t *d_oi;
+        STCHK(ensure(c, "mrgov", G + 1, &d_ov)); STCHK(ensure(c, "mrgoi", G + 1, &d_oi));
+        STCHK(ensure(c, "blist", n / (MTB_BUILD_LANE_MAX + 1) + 2, &d_list));
+        uint32_t *d_nlist = scal<uint32_t>(c, SC_JOIN_COUNT);
+        HIPCHK(scal_clear(c, SC_JOIN_COUNT));
+        hipLaunchKernelGGL(k_build_reduce, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv, d_ov, d_oi, d_list, d_nlist);
+        HIPCHK(hipGetLastError());
+        uint32_t n_long = 0;
+        STCHK(d2h(c, &n_long, d_nlist, 4));
+        if (n_long) {
+            hipLaunchKernelGGL(k_build_reduce_long, dim3(std::min<uint32_t>(n_long, 1u << 16)), dim3(64), 0, st, (const mtb_kmer *)d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv,
+                               d_ov, d_oi, (const uint32_t *)d_list, (const uint32_t *)d_nlist);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        S.ms_reduce += (float)ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        STCHK(w.append(d_ov, d_oi, G));
+        S.ms_encode_write += (float)ms_since(t0);
+        S.n_entries += G;
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    STCHK(w.finish(split_num));
+    S.ms_split = (float)ms_since(t0);
+    S.ms_total = (float)ms_since(t_all);
+    if (stats) *stats = S;
     return MTB_OK;
 }
 
