@@ -581,6 +581,52 @@ mtb_status mtb_merge_databases(mtb_ctx *, const char *const *dbdirs, uint32_t n_
  * (n_a + n_b records; equal records of a come first).  The tile of the merge kernel is 2048 records. */
 mtb_status mtb_merge_sorted(mtb_ctx *, const mtb_kmer *a, uint64_t n_a, const mtb_kmer *b, uint64_t n_b, mtb_kmer *out);
 
+/* ---- audit of a database directory ----
+ * validateDatabase (validateDatabase.cpp:17-142: file presence, #end words of diffIdx == #info entries, "more robust validation will
+ * be implemented in the future") extended to everything mtb_index_open, the joins and the readers that start at `split` checkpoints
+ * assume, in ONE streaming pass: diffIdx is decoded chunk_words 16-bit words at a time (the decode of mtb_index_open, with its carry)
+ * and every chunk is checked and counted on the device; the index is never resident.  Peak device memory: one chunk's words, values
+ * and info entries, the taxonomy and the bins (8 x 4 B per taxonomy id), whatever the size of the database.
+ * Report: every first_* field is an entry index (first_bad_checkpoint: the record's index in `split`) and UINT64_MAX when its count
+ * is 0.  Entries are audited while both files have them: n_entries = min(n_end_words, n_info_entries).  Ids are info & info_mask
+ * (bit 31 masked for Skip_redundancy 0 databases, as everywhere).  species = the table mtb_index_open builds (mtb_tax_species); an
+ * unknown id has species 0 in the order checks.
+ * Checkpoints: the records merge_input_from_split (host/merge_plan.h) would let a reader start from; record {ad, diff_off, info_off}
+ * is good iff words [0, diff_off) hold exactly info_off end words, word diff_off - 1 is an end word and value[info_off - 1] == ad.
+ *   valid     = n_end_words == n_info_entries and n_trailing_words, n_value_descents, n_unknown_ids, n_bad_checkpoints all 0
+ *   canonical = valid and n_group_disorder == 0 and n_unlisted_ids == 0: what mtb_builder_finish + mtb_index_write and
+ *               mtb_merge_databases promise; a legacy database (Skip_redundancy 0) may be valid and not canonical.
+ * species_counts (host, may be NULL; cap entries, at least mtb_tax_max_id + 1): species_counts[s] = audited entries whose id is
+ * known and has species s -- DBDIR/sp2uniqKmerCnt of the reference (Classifier.cpp:390-440), u32 like there, with two departures:
+ * the reference stops counting at the first zero info entry (:419) and does not mask bit 31.
+ * Status: the files are checked first, before any device work, in validateDatabase.cpp's order and wording (missing diffIdx / info /
+ * split / taxID_list, no taxonomy, an empty diffIdx or info, a size that is no multiple of 2 / 4): MTB_ERR_IO, mtb_last_error() names
+ * the file (a missing db.parameters is only noted behind such a message).  Reduced_alphabet 1: MTB_ERR_UNSUPPORTED.  cap too small:
+ * MTB_ERR_CAPACITY, the message gives the entries needed, out->n_species holds them too, nothing else is written.  An entry of
+ * more than five words cannot be decoded: MTB_ERR_IO.  A database that is merely unsound returns MTB_OK with valid = 0.
+ * Times: host-clock ms of the file reads (they overlap the device), device ms of decode / checks (events), ms_hist = clearing,
+ * summing (one bin array per XCD) and downloading the bins (the counting itself is fused into the check kernel), ms_total = the call. */
+typedef struct {
+    uint64_t n_words, n_end_words, n_trailing_words;   /* 16-bit words of diffIdx; words with 0x8000; words behind the last end word */
+    uint64_t n_info_entries, n_entries;                /* info file size / 4; entries audited = min(n_end_words, n_info_entries) */
+    uint64_t n_value_descents,  first_value_descent;   /* entry i with value[i] <  value[i-1] */
+    uint64_t n_group_disorder,  first_group_disorder;  /* value[i] == value[i-1] and species[i] <= species[i-1] */
+    uint64_t n_unknown_ids,     first_unknown_id;      /* (info & info_mask) not in the taxonomy after merged.dmp aliasing */
+    uint64_t n_unlisted_ids,    first_unlisted_id;     /* known to the taxonomy, absent from taxID_list */
+    uint64_t n_no_species;                             /* known id whose taxId2speciesId is 0: not counted for any species */
+    uint64_t n_checkpoints, n_bad_checkpoints, first_bad_checkpoint;   /* usable records of split (merge_input_from_split's rule) */
+    uint64_t n_species;                                /* species with a count > 0 */
+    uint64_t n_chunks;
+    int32_t  valid, canonical;
+    float    ms_read, ms_decode, ms_check, ms_hist, ms_total;
+} mtb_audit_report;
+mtb_status mtb_database_audit(mtb_ctx *, const char *dbdir, const char *taxonomy_dir /* as mtb_index_open */,
+                              mtb_params *params /* in/out, as mtb_index_open */, uint64_t chunk_words /* 0: from the workspace limit / free HBM */,
+                              uint32_t *species_counts /* host, may be NULL */, uint64_t cap /* entries; need mtb_tax_max_id + 1 */,
+                              mtb_audit_report *out);
+/* DBDIR/sp2uniqKmerCnt as Classifier.cpp:433-437 writes it: one "<id> <count>\n" per non-zero count, ids ascending */
+mtb_status mtb_audit_write_species_counts(const char *dbdir, const uint32_t *species_counts, uint64_t n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -200,5 +200,22 @@ inline mtb_merge_stats mergeDatabases(mtb_ctx *ctx, const std::vector<std::strin
     return st;
 }
 
+/* validateDatabase (validateDatabase.cpp:17-142) and the per-species entry counts of Classifier::countUniqueKmerPerSpecies
+ * (Classifier.cpp:390-440) in one streaming pass: mtb_database_audit.  speciesCounts (may be NULL) is sized to the taxonomy here.
+ * A database that is merely unsound is reported (valid = 0), not thrown. */
+inline mtb_audit_report auditDatabase(mtb_ctx *ctx, const std::string &dbDir, const std::string &taxonomyDir, LocalParameters par,
+                                      std::vector<uint32_t> *speciesCounts = nullptr, uint64_t chunkWords = 0) {
+    mtb_audit_report r;
+    const char *tax = taxonomyDir.empty() ? nullptr : taxonomyDir.c_str();
+    if (speciesCounts) {
+        uint32_t none = 0;
+        const mtb_status q = mtb_database_audit(ctx, dbDir.c_str(), tax, &par, chunkWords, &none, 0, &r);       /* refused before any device work: r.n_species = entries needed */
+        if (q != MTB_ERR_CAPACITY) check(q);
+        speciesCounts->assign((size_t)r.n_species, 0);
+    }
+    check(mtb_database_audit(ctx, dbDir.c_str(), tax, &par, chunkWords, speciesCounts ? speciesCounts->data() : nullptr, speciesCounts ? speciesCounts->size() : 0, &r));
+    return r;
+}
+
 } // namespace mtb
 #endif

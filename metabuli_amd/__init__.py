@@ -244,6 +244,25 @@ class Context:
                                         C.c_int(split_num), C.c_uint64(int(max_range_records)), C.byref(s)))
         return {name: (float(getattr(s, name)) if name.startswith("ms_") else int(getattr(s, name))) for name, _ in MergeStats._fields_}
 
+    def audit_database(self, dbdir, taxonomy_dir=None, params=None, chunk_words=0, counts=True):
+        """mtb_database_audit: one streaming pass over a database directory of any size -> (the report as a dict, the per-species entry
+        counts as a uint32 array indexed by species id, or None without `counts`).  A database that is merely unsound is reported
+        (valid = 0), not raised; params (default_params() if None) receives what db.parameters says, as for open_index."""
+        params = params if params is not None else default_params()
+        r = AuditReport()
+        args = (self.h, dbdir.encode(), taxonomy_dir.encode() if taxonomy_dir else None, C.byref(params), C.c_uint64(int(chunk_words)))
+        arr = None
+        if counts:
+            # the array's size is the taxonomy's largest id + 1: an array without room is refused with that number, before any device work
+            one = np.zeros(1, np.uint32)
+            st = self.L.mtb_database_audit(*args, _p(one), C.c_uint64(0), C.byref(r))
+            if st != MTB_ERR_CAPACITY:
+                _chk(st)
+            arr = np.zeros(int(r.n_species), np.uint32)
+        _chk(self.L.mtb_database_audit(*args, _p(arr), C.c_uint64(len(arr) if counts else 0), C.byref(r)))
+        rep = {name: (float(getattr(r, name)) if name.startswith("ms_") else int(getattr(r, name))) for name, _ in AuditReport._fields_}
+        return rep, arr
+
     def merge_sorted(self, a, b):
         """mtb_merge_sorted (stage call of the merge kernels): two kmer_dt lists, each ascending in (value, qinfo) -> their merge"""
         a = np.ascontiguousarray(a, dtype=kmer_dt); b = np.ascontiguousarray(b, dtype=kmer_dt)
@@ -529,6 +548,20 @@ class MergeStats(C.Structure):
 
 
 MERGE_TILE = 2048          # records per tile of the merge kernel (MTB_MERGE_TILE, kernels_merge.h)
+
+
+class AuditReport(C.Structure):
+    """mtb_audit_report (include/mtb.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_words", "n_end_words", "n_trailing_words", "n_info_entries", "n_entries", "n_value_descents", "first_value_descent",
+                                          "n_group_disorder", "first_group_disorder", "n_unknown_ids", "first_unknown_id", "n_unlisted_ids", "first_unlisted_id",
+                                          "n_no_species", "n_checkpoints", "n_bad_checkpoints", "first_bad_checkpoint", "n_species", "n_chunks")] + \
+               [("valid", C.c_int32), ("canonical", C.c_int32)] + [(n, C.c_float) for n in ("ms_read", "ms_decode", "ms_check", "ms_hist", "ms_total")]
+
+
+def write_species_counts(dbdir, counts):
+    """DBDIR/sp2uniqKmerCnt from the counts of Context.audit_database (mtb_audit_write_species_counts)"""
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    _chk(lib().mtb_audit_write_species_counts(dbdir.encode(), _p(counts), C.c_uint64(len(counts))))
 
 BUILD_STAGES = ["keys", "sort_key", "sort_value", "heads_scan", "reduce", "total"]
 

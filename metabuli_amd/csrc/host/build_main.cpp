@@ -19,7 +19,11 @@
  * streams them together): when the builder holds --max-records N records (default: what mtb_builder_capacity reports for this
  * device, below 2^32) it is finished and written to OUTDB/tmp_parts/part_K, and at the end the parts and every --add-db database --
  * which then never enter a builder -- are merged by mtb_merge_databases, one value range at a time; tmp_parts is removed.  A pure
- * merge (GENOMES `-`) always takes that route.  A build that fits takes the in-memory one; the files are the same either way. */
+ * merge (GENOMES `-`) always takes that route.  A build that fits takes the in-memory one; the files are the same either way.
+ *
+ *   mtb_build --audit 1 - - TAXONOMYDIR DBDIR      audit only (mtb_database_audit): the report is printed, DBDIR/sp2uniqKmerCnt (the
+ *             reference's per-species entry counts, Classifier.cpp:390-440) is written, exit 1 if the database is not valid
+ *   --validate-db 1 on any build, update or merge: OUTDB is audited after it is written; the run fails if it is not canonical */
 #include <dirent.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -36,6 +40,7 @@
 #include "../../../include/mtb.h"
 #include "fastx.h"
 #include "cds_info.h"
+#include "audit_plan.h"
 
 static void die(const std::string &m) { throw std::runtime_error(m); }
 static void chk(mtb_status s, const char *what) { if (s != MTB_OK) die(std::string(what) + ": " + mtb_last_error()); }
@@ -72,9 +77,34 @@ static void copy_file(const std::string &from, const std::string &to) {
     if (!out) die("short write to " + to);
 }
 
+/* mtb_database_audit of `db` with its report printed; counts: also DBDIR/sp2uniqKmerCnt */
+static mtb_audit_report audit(mtb_ctx *ctx, const std::string &db, const std::string &taxdir, mtb_params par, bool counts) {
+    printf("Validating database: %s\n", db.c_str());
+    std::vector<uint32_t> cnt;
+    mtb_audit_report r;
+    if (counts) {       /* the array's size is the taxonomy's: an array without room is refused with that number before any device work */
+        uint32_t none = 0;
+        const mtb_status q = mtb_database_audit(ctx, db.c_str(), taxdir.c_str(), &par, 0, &none, 0, &r);
+        if (q != MTB_ERR_CAPACITY) chk(q, ("audit " + db).c_str());
+        cnt.assign((size_t)r.n_species, 0);
+    }
+    const mtb_status s = mtb_database_audit(ctx, db.c_str(), taxdir.c_str(), &par, 0, counts ? cnt.data() : nullptr, cnt.size(), &r);
+    chk(s, ("audit " + db).c_str());
+    mtbhost::audit_print_counts(stdout, stderr, r);
+    mtbhost::audit_print_findings(stderr, r);
+    printf("Audited: %llu entries in %llu chunks, %llu checkpoints (%llu bad), %llu species, %llu ids without a species; valid %d, canonical %d; "
+           "read %.1f ms, decode %.1f ms, check %.1f ms, counts %.1f ms, total %.1f ms\n",
+           (unsigned long long)r.n_entries, (unsigned long long)r.n_chunks, (unsigned long long)r.n_checkpoints, (unsigned long long)r.n_bad_checkpoints,
+           (unsigned long long)r.n_species, (unsigned long long)r.n_no_species, r.valid, r.canonical, r.ms_read, r.ms_decode, r.ms_check, r.ms_hist, r.ms_total);
+    if (counts) chk(mtb_audit_write_species_counts(db.c_str(), cnt.data(), cnt.size()), "write sp2uniqKmerCnt");
+    fflush(stdout);
+    return r;
+}
+
 int main(int argc, char **argv) {
     try {
         std::vector<std::string> add_db, pos;
+        bool audit_only = false, validate_db = false;
         std::string cds_list;
         int split_num = 4096, device = 0;
         unsigned long long max_records = 0;          /* 0: from the device */
@@ -92,15 +122,25 @@ int main(int argc, char **argv) {
             else if (a == "--smer-len") par.smer_len = atoi(val().c_str());
             else if (a == "--kmer-format") par.kmer_format = atoi(val().c_str());
             else if (a == "--device") device = atoi(val().c_str());
+            else if (a == "--audit") audit_only = atoi(val().c_str()) != 0;
+            else if (a == "--validate-db") validate_db = atoi(val().c_str()) != 0;
             else if (a.size() > 2 && a.rfind("--", 0) == 0) die("unknown flag " + a);
             else pos.push_back(a);
         }
         if (pos.size() != 4) {
             fprintf(stderr, "usage: mtb_build [--add-db OLDDB]... [--cds-info LIST] [--max-records N] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d] "
-                            "GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB\n");
+                            "[--validate-db 0|1] GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB\n       mtb_build --audit 1 [--device d] - - TAXONOMYDIR DBDIR\n");
             return 1;
         }
         const std::string genomes = pos[0], map_path = pos[1], taxdir = pos[2], outdb = pos[3];
+        if (audit_only) {
+            mtb_ctx *actx = nullptr;
+            chk(mtb_ctx_create(device, nullptr, &actx), "mtb_ctx_create");
+            const mtb_audit_report r = audit(actx, outdb, taxdir, par, true);
+            mtb_ctx_destroy(actx);
+            if (!r.valid) { fprintf(stderr, "Database validation failed.\n"); return 1; }
+            return 0;
+        }
         if (genomes == "-" && add_db.empty()) die("nothing to build: no genomes and no --add-db");
         if (split_num < 2) die("--split-num must be at least 2");
         if (!cds_list.empty() && par.kmer_format != 2) die("--cds-info needs --kmer-format 2 (block extraction implements no other)");
@@ -268,8 +308,13 @@ int main(int argc, char **argv) {
                             "%llu joined CDS, %llu non-CDS regions --, %llu sequences without a CDS entry in six frames; no gene prediction, no masking)\n",
                     n_seqs, n_bases, n_rec, n_entries, outdb.c_str(), route, n_by_blocks, n_cds_single, n_cds_joined, n_noncds, n_six_frames);
         mtb_builder_destroy(bld);
+        bool sound = true;
+        if (validate_db) {
+            sound = audit(ctx, outdb, taxdir, par, false).canonical != 0;
+            if (!sound) fprintf(stderr, "mtb_build: %s is not a canonical database\nDatabase validation failed.\n", outdb.c_str());
+        }
         mtb_ctx_destroy(ctx);
-        return 0;
+        return sound ? 0 : 1;
     } catch (const std::exception &e) {
         fprintf(stderr, "mtb_build: %s\n", e.what());
         return 1;

@@ -16,8 +16,10 @@
  *          --lineage 0|1  --threads N (host parsing / formatting)
  *   accepted for command-line compatibility, no effect here (one warning each): --max-ram (batches are bounded by HBM inside
  *          the library; the host batch is --max-reads), --match-per-kmer (exact-size retry), --hamming-margin and --max-gap (stored
- *          but never read by the reference's classify path either), --mask 0, --mask-prob, --validate-input, --validate-db,
+ *          but never read by the reference's classify path either), --mask 0, --mask-prob, --validate-input, --validate-db 0,
  *          --print-log, -v   (LocalParameters.cpp:631-654).  Refused: --mask 1, --reduced-aa 1 (they change the answers)
+ *   --validate-db 1: the database is audited before it is opened (mtb_database_audit: validateDatabase.cpp's file and count checks,
+ *          value order, ids against the taxonomy, every split checkpoint); exit 1 with "Database validation failed." if it is not valid
  *   filter mode (`metabuli filter`, src/workflow/filter.cpp:5-45, QueryFilter.cpp:75-186): --filter 1 [--print-mode 1|2] <FASTA/Q> [<mate>] <DBDIR>
  *          classifies with the filter command's defaults (--min-score 0.5 unless given) and writes, next to the input,
  *          <base>_filtered.fna (reads NOT classified = not contamination), with --print-mode 2 also <base>_removed.fna (classified
@@ -57,6 +59,7 @@
 #include "../mtb_core.h"         /* mtb_build_tables: the extractor's base classes, for the 2-bit packing of the reads */
 #include "fastx.h"
 #include "format.h"
+#include "audit_plan.h"
 
 namespace {
 
@@ -259,6 +262,49 @@ void write_krona(FILE *fp, const CladeTable &ct, unsigned long total) {
     fputs("</node></krona></div></body></html>", fp);
 }
 
+/* --validate-db 1: validateDatabase (validateDatabase.cpp:17-142) with its progress lines, carried out by mtb_database_audit -- the
+ * reference's two checks (files present, #end words == #info entries) and everything the audit adds, one line per finding.  The
+ * files are checked before a device is touched.  false: the database is not valid (or could not be audited). */
+} // namespace
+/* An engine that implements the classification part of the C ABI alone (a stand-in library linked in place of libmtb.so) need not
+ * have the audit: the reference is weak, and --validate-db 1 is refused where it is absent. */
+extern "C" mtb_status mtb_database_audit(mtb_ctx *, const char *, const char *, mtb_params *, uint64_t, uint32_t *, uint64_t, mtb_audit_report *) __attribute__((weak));
+namespace {
+bool validate_database(const std::string &dbdir, const std::string &taxdir, mtb_params par, int device) {
+    printf("Validating database: %s\n", dbdir.c_str());
+    printf("Check if required files exist...\n");
+    fflush(stdout);
+    mtbhost::AuditFiles files; std::string err;
+    if (!mtbhost::audit_check_files(dbdir, taxdir.empty() ? nullptr : taxdir.c_str(), &files, &err)) {
+        if (!files.note.empty()) fprintf(stderr, "%s\n", files.note.c_str());
+        if (files.all_present) printf("All required files are present.\nCheck if the k-mer count and k-mer ID count are consistent...\n");
+        fflush(stdout);
+        fprintf(stderr, "%s\nDatabase validation failed.\n", err.c_str());
+        return false;
+    }
+    if (!files.note.empty()) fprintf(stderr, "%s\n", files.note.c_str());
+    printf("All required files are present.\n");
+    printf("Check if the k-mer count and k-mer ID count are consistent...\n");
+    fflush(stdout);
+    if (!mtb_database_audit) { fprintf(stderr, "mtb_classify: --validate-db 1: this engine has no mtb_database_audit\nDatabase validation failed.\n"); return false; }
+    mtb_ctx *ctx = nullptr;
+    mtb_audit_report r;
+    mtb_status s = mtb_ctx_create(device, nullptr, &ctx);
+    if (s == MTB_OK) { s = mtb_database_audit(ctx, dbdir.c_str(), taxdir.empty() ? nullptr : taxdir.c_str(), &par, 0, nullptr, 0, &r); }
+    const std::string msg = s == MTB_OK ? std::string() : std::string(mtb_last_error());
+    if (ctx) mtb_ctx_destroy(ctx);
+    if (s != MTB_OK) { fprintf(stderr, "mtb_classify: --validate-db: %s\nDatabase validation failed.\n", msg.c_str()); return false; }
+    mtbhost::audit_print_counts(stdout, stderr, r);
+    mtbhost::audit_print_findings(stderr, r);
+    if (!r.valid) { fprintf(stderr, "Database validation failed.\n"); return false; }
+    printf("Database validation completed successfully.\n    It does not guarantee that the database is completely valid.\n"
+           "    More robust validation will be implemented in the future.\n");
+    printf("    Audited: %llu entries in %llu chunks, %llu checkpoints, %llu species%s.\n", (unsigned long long)r.n_entries, (unsigned long long)r.n_chunks,
+           (unsigned long long)r.n_checkpoints, (unsigned long long)r.n_species, r.canonical ? "; canonical" : "; valid, not canonical");
+    fflush(stdout);
+    return true;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -267,6 +313,7 @@ int main(int argc, char **argv) {
     int threads = (int)std::max(1u, std::min(128u, std::thread::hardware_concurrency()));
     bool lineage = false, filter = false, min_score_given = false, partitioned = false, pack = true, async_results = false; int print_mode = 1, gpu_workers = 1;
     std::vector<std::string> pos;
+    bool validate_db = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(1); } return std::string(argv[++i]); };
@@ -296,6 +343,7 @@ int main(int argc, char **argv) {
         else if (a == "--max-ram" || a == "--match-per-kmer" || a == "--hamming-margin" || a == "--mask-prob" ||
                  a == "--validate-input" || a == "--validate-db" || a == "--print-log" || a == "-v" || a == "--max-gap") {
             std::string v = val();
+            if (a == "--validate-db" && atoi(v.c_str()) != 0) { validate_db = true; continue; }      /* the database is audited before it is opened */
             fprintf(stderr, "mtb_classify: %s %s accepted for compatibility with `metabuli classify`, it has no effect here\n", a.c_str(), v.c_str());
         }
         else if (a == "--threads") threads = std::max(1, atoi(val().c_str()));
@@ -313,6 +361,7 @@ int main(int argc, char **argv) {
     if (partitioned) { pack = false; gpu_workers = 1; }        /* (the partitioned batch takes the text; its engines work on one batch together) */
     if (!pack || partitioned || devices.size() != 1) async_results = false;      /* (one engine per worker, packed reads: mtb_classify_batch_packed_async) */
     const std::string dbdir = pos[paired ? 2 : 1];
+    if (validate_db && !validate_database(dbdir, taxdir, par, devices.empty() ? 0 : devices[0])) return 1;
     /* classify: <OUTDIR>/<JobID>_*; filter: <base of the first input>_* (QueryFilter.cpp:75-93) */
     const std::string base1 = filter ? query_base_name(pos[0]) : std::string(), base2 = filter && paired ? query_base_name(pos[1]) : std::string();
     const std::string prefix = filter ? base1 : pos[paired ? 3 : 2] + "/" + pos[paired ? 4 : 3];

@@ -20,12 +20,14 @@
 #include "../../include/mtb.h"
 #include "host_db.h"
 #include "host/merge_plan.h"
+#include "host/audit_plan.h"
 #include "kernels_extract.h"
 #include "kernels_extract_blocks.h"
 #include "kernels_index.h"
 #include "kernels_join.h"
 #include "kernels_build.h"
 #include "kernels_merge.h"
+#include "kernels_audit.h"
 #include "kernels_dir.h"
 #include "kernels_scan.h"
 #include "kernels_score.h"
@@ -116,6 +118,7 @@ struct ExtractCounters { uint64_t records /* allocated, incl. blank tails */, ov
 static_assert(sizeof(ExtractCounters) == 8 * (SC_WIN_STATS - SC_EXTRACT) && SC_WIN_STATS + 2 <= SC_N_UNGROUPED && SC_SCORE_WORK + 2 <= SC_LONG_WORK && SC_OPEN_FLAGS < SC_WORDS, "scalar names overlap or leave the block");
 struct mtb_ctx {
     int device = 0;
+    int audit_mode = 0;              /* mtb_debug_audit_mode (measurements): how mtb_database_audit takes the species counts */
     hipStream_t stream = nullptr;
     mtb_tables *d_tabs = nullptr;
     mtb_tables h_tabs;
@@ -1386,7 +1389,26 @@ static mtb_status stream_file_to_device(mtb_ctx *c, const std::string &path, uin
  * On return *dir_ok says whether the directory is usable (else it has been freed); with `pack` a false *dir_ok is an error to the
  * caller (the array is partly packed): it opens again without. */
 struct OpenPlan { uint64_t n16 = 0, T = 0, expect = 0, lead = 0, diff_off = 0, info_off = 0, first_value = 0; };
-static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d, const OpenPlan &P, bool want_dir, int L, bool pack, bool *dir_ok) {
+/* A caller that looks at every decoded chunk instead of keeping the array (mtb_database_audit): with a sink, value[] and info[] of the
+ * index are CHUNK buffers (chunk_words + 9 values, as many info entries) that every chunk overwrites, the number of entries is
+ * whatever the words hold (P.expect is not consulted; info entries are read while the file has them: P.T) and on_chunk runs on
+ * the stream behind each chunk's decode, before the buffers are reused. */
+struct DecodedChunk {
+    const uint16_t *d_words; uint64_t n_words, word0;      /* the chunk's words and the file offset (in words, from P.diff_off) of the first */
+    const uint64_t *d_tile_off;                            /* end words before each 2048-word tile of the chunk (and, last, all of them) */
+    const uint64_t *d_values; uint64_t n_values;           /* entries first_entry .. first_entry + n_values */
+    const uint32_t *d_info; uint64_t n_info;               /* info entries of the first n_info of them */
+    uint64_t first_entry;
+};
+struct ChunkSink {
+    uint64_t chunk_words = 0;                              /* 0: decode_chunked's own choice */
+    std::function<mtb_status(const DecodedChunk &)> on_chunk;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};        /* recorded before a chunk's upload, behind its decode, behind on_chunk */
+    uint64_t n_entries = 0, n_chunks = 0;
+    std::atomic<uint64_t> us_read{0};                      /* host clock inside the file reads (they overlap the device) */
+    float ms_decode = 0, ms_sink = 0;
+};
+static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d, const OpenPlan &P, bool want_dir, int L, bool pack, bool *dir_ok, ChunkSink *sink = nullptr) {
     *dir_ok = false;
     hipStream_t st = c->stream;
     /* 16-bit words per chunk: 128 M (256 MB), less when the context's workspace limit asks for it (a chunk costs ~16 bytes per word:
@@ -1394,6 +1416,13 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
     uint64_t CH = 128ull << 20;
     if (c->ws_limit) CH = std::max<uint64_t>(1u << 16, std::min<uint64_t>(CH, c->ws_limit / 16));
     if (c->opt.open_chunk > 0) CH = std::max<uint64_t>(16, (uint64_t)c->opt.open_chunk);
+    if (sink && sink->chunk_words) CH = std::max<uint64_t>(16, sink->chunk_words);
+    auto timed_read = [sink](int fd, void *dst, uint64_t off, size_t len, int n_threads) {
+        const auto t0 = std::chrono::steady_clock::now();
+        const bool ok = pread_parallel(fd, dst, off, len, n_threads);
+        if (sink) sink->us_read += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+        return ok;
+    };
     const int fmt = ix->params.kmer_format;
     const uint32_t nbk = want_dir ? mtb_pow21(L) : 0, n_groups = want_dir ? (nbk >> 16) + 1 : 0;
     uint32_t *d_flags = scal<uint32_t>(c, SC_OPEN_FLAGS);
@@ -1437,13 +1466,13 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
     uint16_t carry_w[8]; uint32_t n_carry = 0;
     /* the first chunk is read here, every further one by a helper thread while the device works on its predecessor */
     uint64_t cur_new = std::min<uint64_t>(chunk_words, P.n16);
-    if (cur_new && !pread_parallel(fd_d, pin.p[0], (P.diff_off + done_words) * 2, cur_new * 2, 16)) return fail(MTB_ERR_IO, "short read from " + d + "/diffIdx");
+    if (cur_new && !timed_read(fd_d, pin.p[0], (P.diff_off + done_words) * 2, cur_new * 2, 16)) return fail(MTB_ERR_IO, "short read from " + d + "/diffIdx");
     int cur = 0;
     while (done_words < P.n16) {
         const uint64_t next_off = done_words + cur_new, next_new = std::min<uint64_t>(chunk_words, P.n16 - next_off);
         bool next_ok = true;
         std::thread reader;
-        if (next_new) reader = std::thread([&, next_off, next_new] { next_ok = pread_parallel(fd_d, pin.p[cur ^ 1], (P.diff_off + next_off) * 2, next_new * 2, 16); });
+        if (next_new) reader = std::thread([&, next_off, next_new] { next_ok = timed_read(fd_d, pin.p[cur ^ 1], (P.diff_off + next_off) * 2, next_new * 2, 16); });
         struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join_reader{reader};
         const uint16_t *hw = (const uint16_t *)pin.p[cur];
         /* words of a metamer cut by this chunk's end stay for the next one */
@@ -1452,6 +1481,7 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
         if (tail == cur_new && cur_new < 5) { /* (a chunk of fewer than five words without a terminator: all of it is carried) */ }
         if (tail >= 5 || (next_new == 0 && tail != 0)) return fail(MTB_ERR_IO, "diffIdx is corrupt: a metamer without its terminator word");
         const uint64_t use_new = cur_new - tail, n_use = n_carry + use_new;
+        if (sink) HIPCHK(hipEventRecord(sink->ev[0], st));
         if (n_carry) HIPCHK(hipMemcpyAsync(d_chunk, carry_w, n_carry * 2, hipMemcpyHostToDevice, st));
         if (use_new) HIPCHK(hipMemcpyAsync(d_chunk + n_carry, hw, use_new * 2, hipMemcpyHostToDevice, st));
         uint64_t n_k = 0;
@@ -1460,27 +1490,42 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
             hipLaunchKernelGGL(k_diff_tile_count, dim3((uint32_t)tiles), dim3(256), 0, st, (const uint16_t *)d_chunk, n_use, d_tc);
             scan_launch<uint32_t, uint64_t, false>(st, d_tc, tiles, true, d_toff, d_ws);
             STCHK(d2h(c, &n_k, d_toff + tiles, 8));
-            if (found + n_k > P.expect) return fail(MTB_ERR_IO, "diffIdx holds more metamers than info and split announce (" + std::to_string(P.expect) + ")");
+            if (!sink && found + n_k > P.expect) return fail(MTB_ERR_IO, "diffIdx holds more metamers than info and split announce (" + std::to_string(P.expect) + ")");
             if (n_k) {
                 const uint64_t m = std::min<uint64_t>(g + n_k, P.T) - std::min<uint64_t>(g, P.T);       /* entries of the chunk that belong to the index (a dropped last one does not) */
+                const uint64_t at = sink ? 0 : g;                  /* where the chunk goes in value[] / info[] */
                 /* info entries of the chunk: into the chunk buffer (pack) or straight to their places */
                 if (m) {
-                    if (!pread_parallel(fd_i, pin.p[2], (P.info_off + g) * 4, m * 4, 16)) return fail(MTB_ERR_IO, "short read from " + d + "/info");
-                    HIPCHK(hipMemcpyAsync(pack ? d_ichunk : ix->d_info + g, pin.p[2], m * 4, hipMemcpyHostToDevice, st));
+                    if (!timed_read(fd_i, pin.p[2], (P.info_off + g) * 4, m * 4, 16)) return fail(MTB_ERR_IO, "short read from " + d + "/info");
+                    HIPCHK(hipMemcpyAsync(pack ? d_ichunk : ix->d_info + at, pin.p[2], m * 4, hipMemcpyHostToDevice, st));
                 }
-                hipLaunchKernelGGL(k_diff_assemble, dim3((uint32_t)tiles), dim3(256), 0, st, (const uint16_t *)d_chunk, n_use, (const uint64_t *)d_toff, ix->d_values + g);
-                hipLaunchKernelGGL(k_diff_add_carry, dim3(1), dim3(1), 0, st, ix->d_values + g, (const uint64_t *)d_carry);
-                scan_launch<uint64_t, uint64_t, true>(st, ix->d_values + g, n_k, false, ix->d_values + g, d_ws);
+                hipLaunchKernelGGL(k_diff_assemble, dim3((uint32_t)tiles), dim3(256), 0, st, (const uint16_t *)d_chunk, n_use, (const uint64_t *)d_toff, ix->d_values + at);
+                hipLaunchKernelGGL(k_diff_add_carry, dim3(1), dim3(1), 0, st, ix->d_values + at, (const uint64_t *)d_carry);
+                scan_launch<uint64_t, uint64_t, true>(st, ix->d_values + at, n_k, false, ix->d_values + at, d_ws);
                 if (want_dir && m) {
                     const dim3 grid((uint32_t)std::min<uint64_t>((m + 255) / 256, 1u << 16));
                     hipLaunchKernelGGL(k_dir_chunk_base, grid, dim3(256), 0, st, (const uint64_t *)ix->d_values, g, m, (const uint64_t *)d_carry, L, fmt, nbk, ix->d_dirbase, d_flags);
                     hipLaunchKernelGGL(k_dir_chunk_fill, grid, dim3(256), 0, st, (const uint64_t *)ix->d_values, g, m, (const uint64_t *)d_carry, L, fmt, nbk,
                                        (const uint64_t *)ix->d_dirbase, ix->d_dir, d_flags);
                 }
-                hipLaunchKernelGGL(k_save_last, dim3(1), dim3(1), 0, st, (const uint64_t *)(ix->d_values + g + n_k - 1), d_carry);
+                hipLaunchKernelGGL(k_save_last, dim3(1), dim3(1), 0, st, (const uint64_t *)(ix->d_values + at + n_k - 1), d_carry);
+                if (sink) {
+                    HIPCHK(hipEventRecord(sink->ev[1], st));
+                    DecodedChunk ck;
+                    ck.d_words = d_chunk; ck.n_words = n_use; ck.word0 = done_words - n_carry; ck.d_tile_off = d_toff;
+                    ck.d_values = ix->d_values; ck.n_values = n_k; ck.d_info = ix->d_info; ck.n_info = m; ck.first_entry = g;
+                    STCHK(sink->on_chunk(ck));
+                    HIPCHK(hipEventRecord(sink->ev[2], st));
+                }
                 if (pack && m) hipLaunchKernelGGL(k_index_pack_chunk, dim3((uint32_t)std::min<uint64_t>((m + 255) / 256, 1u << 16)), dim3(256), 0, st, ix->d_values, (const uint32_t *)d_ichunk, g, m, fmt);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(st));          /* the pinned buffers are refilled next */
+                if (sink) {
+                    float ms = 0;
+                    HIPCHK(hipEventElapsedTime(&ms, sink->ev[0], sink->ev[1])); sink->ms_decode += ms;
+                    HIPCHK(hipEventElapsedTime(&ms, sink->ev[1], sink->ev[2])); sink->ms_sink += ms;
+                    sink->n_chunks++;
+                }
                 g += n_k; found += n_k;
                 if (ix->open_chunks < 4 || (ix->open_chunks & 63u) == 0) {        /* (a driver query: not for every one of thousands of tiny test chunks) */
                     size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess && ix->open_free0 > fr) ix->open_peak_bytes = std::max<uint64_t>(ix->open_peak_bytes, ix->open_free0 - fr); }
@@ -1495,7 +1540,8 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
         if (!next_ok) return fail(MTB_ERR_IO, "short read from " + d + "/diffIdx");
         done_words = next_off; cur_new = next_new; cur ^= 1;
     }
-    if (found != P.expect)    /* validateDatabase.cpp:17-142: #terminators must equal #info entries */
+    if (sink) sink->n_entries = found;
+    else if (found != P.expect)    /* validateDatabase.cpp:17-142: #terminators must equal #info entries */
         return fail(MTB_ERR_IO, "diffIdx holds " + std::to_string(found) + " metamers where info and split announce " + std::to_string(P.expect));
     if (want_dir) {
         /* (*d_carry = the last decoded value; with a dropped last entry the index's own last flat value is one before it: re-read it) */
@@ -1533,6 +1579,25 @@ static size_t open_make_room(mtb_ctx *c) {
     return fr;
 }
 
+/* the taxonomy of a database directory and its species table (KmerMatcher::loadTaxIdList: built from the ids of taxID_list, which
+ * *ids receives): taxonomyDB if `have_bin` and it loads, else the dump files of `taxdir` (an unreadable taxonomyDB: DBDIR/taxonomy) */
+static mtb_status load_database_taxonomy(const std::string &d, std::string taxdir, bool have_bin, mtbhost::Taxonomy *tax, std::vector<int32_t> *ids) {
+    std::string err;
+    bool tax_ok = false;
+    if (have_bin) {
+        tax_ok = mtbhost::load_taxonomy_db(d + "/taxonomyDB", tax, &err);
+        if (!tax_ok) {
+            const std::string fb = d + "/taxonomy";
+            if (!mtbhost::file_exists(fb + "/nodes.dmp")) return fail(MTB_ERR_IO, err);
+            taxdir = fb; err.clear();
+        }
+    }
+    if (!tax_ok && !mtbhost::load_taxonomy(taxdir, tax, &err)) return fail(MTB_ERR_IO, err);
+    if (!mtbhost::read_taxid_list(d + "/taxID_list", ids)) return fail(MTB_ERR_IO, "cannot open " + d + "/taxID_list");
+    mtbhost::build_tax2species(tax, ids->data(), ids->size());
+    return MTB_OK;
+}
+
 static mtb_status open_impl(mtb_ctx *c, const char *dbdir, const char *taxonomy_dir, mtb_params *params, uint32_t part, uint32_t n_parts, mtb_index **out) {
     if (!c || !dbdir || !params || !out) return fail(MTB_ERR_ARG, "NULL argument");
     if (n_parts == 0 || part >= n_parts) return fail(MTB_ERR_ARG, "partition index out of range");
@@ -1556,20 +1621,8 @@ static mtb_status open_impl(mtb_ctx *c, const char *dbdir, const char *taxonomy_
     struct Guard { mtb_index *ix; ~Guard() { if (ix) mtb_index_close(ix); } } guard{ix};
     ix->ctx = c; ix->params = *params; ix->own = true;
     for (uint32_t q = part + 1; q < n_parts; q++) if (!plan.parts[q].empty) ix->match_last = true;
-    std::string err;
-    bool tax_ok = false;
-    if (have_bin) {
-        tax_ok = mtbhost::load_taxonomy_db(d + "/taxonomyDB", &ix->tax, &err);
-        if (!tax_ok) {
-            const std::string fb = d + "/taxonomy";
-            if (!mtbhost::file_exists(fb + "/nodes.dmp")) return fail(MTB_ERR_IO, err);
-            taxdir = fb; err.clear();
-        }
-    }
-    if (!tax_ok && !mtbhost::load_taxonomy(taxdir, &ix->tax, &err)) return fail(MTB_ERR_IO, err);
     std::vector<int32_t> ids;
-    if (!mtbhost::read_taxid_list(d + "/taxID_list", &ids)) return fail(MTB_ERR_IO, "cannot open " + d + "/taxID_list");
-    mtbhost::build_tax2species(&ix->tax, ids.data(), ids.size());
+    STCHK(load_database_taxonomy(d, taxdir, have_bin, &ix->tax, &ids));
     ix->info_mask = ~((uint32_t)(params->skip_redundancy == 0) << 31);   /* KmerMatcher.cpp:204-205 */
     STCHK(upload_taxonomy(ix));
     if (P.empty) { ix->T = 0; guard.ix = nullptr; *out = ix; return MTB_OK; }
@@ -4225,6 +4278,160 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
     S.ms_split = (float)ms_since(t0);
     S.ms_total = (float)ms_since(t_all);
     if (stats) *stats = S;
+    return MTB_OK;
+}
+
+/* ---- audit of a database directory (mtb.h; kernels_audit.h, host/audit_plan.h) ---- */
+mtb_status mtb_database_audit(mtb_ctx *c, const char *dbdir, const char *taxonomy_dir, mtb_params *params, uint64_t chunk_words, uint32_t *species_counts, uint64_t cap,
+                              mtb_audit_report *out) {
+    if (!c || !dbdir || !params || !out) return fail(MTB_ERR_ARG, "NULL argument");
+    const auto t_all = std::chrono::steady_clock::now();
+    const std::string d(dbdir);
+    /* the files first: nothing below touches the device before they are sound */
+    mtbhost::AuditFiles files;
+    {   std::string err;
+        if (!mtbhost::audit_check_files(d, taxonomy_dir, &files, &err)) return fail(MTB_ERR_IO, d + ": " + err + (files.note.empty() ? "" : " " + files.note)); }
+    auto failed = [&](mtb_status s) { if (!files.note.empty()) g_err += " (" + files.note + ")"; return s; };
+    int reduced_aa = 0;
+    mtbhost::load_db_parameters(d, params, &reduced_aa);
+    if (reduced_aa) return failed(fail(MTB_ERR_UNSUPPORTED, "database was built with the reduced amino-acid alphabet (Reduced_alphabet 1 in db.parameters); not implemented"));
+    if (params->kmer_format != 1 && params->kmer_format != 2) return failed(fail(MTB_ERR_UNSUPPORTED, "database uses a k-mer format other than 1 or 2"));
+    mtb_audit_report R; memset(&R, 0, sizeof(R));
+    R.n_words = files.n_words; R.n_info_entries = files.n_info_entries;
+    R.first_value_descent = R.first_group_disorder = R.first_unknown_id = R.first_unlisted_id = R.first_bad_checkpoint = UINT64_MAX;
+    if (!mtbhost::audit_trailing_words(d + "/diffIdx", R.n_words, &R.n_trailing_words)) return failed(fail(MTB_ERR_IO, "cannot read " + d + "/diffIdx"));
+    std::vector<mtbhost::MergeCheckpoint> split;
+    if (!mtbhost::read_whole(d + "/split", &split)) return failed(fail(MTB_ERR_IO, "cannot read " + d + "/split"));
+    const std::vector<mtbhost::AuditCheckpoint> cps = mtbhost::audit_usable_checkpoints(split, R.n_info_entries, R.n_words);
+    R.n_checkpoints = cps.size();
+    /* the taxonomy and species table of mtb_index_open, on the device: a holder index without targets */
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    mtb_index *hold = new mtb_index();
+    struct Guard { mtb_index *ix; ~Guard() { mtb_index_close(ix); } } guard{hold};
+    hold->ctx = c; hold->params = *params; hold->own = true;
+    std::vector<int32_t> ids;
+    {   const std::string taxdir = taxonomy_dir && *taxonomy_dir ? std::string(taxonomy_dir) : d + "/taxonomy";
+        const mtb_status s = load_database_taxonomy(d, taxdir, mtbhost::file_exists(d + "/taxonomyDB"), &hold->tax, &ids);
+        if (s != MTB_OK) return failed(s); }
+    const uint64_t n_bins = (uint64_t)hold->tax.max_id + 1;
+    if (species_counts && cap < n_bins) {
+        out->n_species = n_bins;
+        return failed(fail(MTB_ERR_CAPACITY, "species_counts holds " + std::to_string(cap) + " entries, the taxonomy needs " + std::to_string(n_bins)));
+    }
+    hold->info_mask = ~((uint32_t)(params->skip_redundancy == 0) << 31);
+    STCHK(upload_taxonomy(hold));
+    const mtb_tax_view tv = tax_view(hold);
+    /* chunk size: the caller's, else the decode's rule (128 M words, less under a workspace limit) within a 32nd of free HBM (a
+     * chunk holds ~16 bytes per word on the device) */
+    uint64_t CH = chunk_words;
+    if (CH == 0) {
+        CH = 128ull << 20;
+        if (c->ws_limit) CH = std::max<uint64_t>(1u << 16, std::min<uint64_t>(CH, c->ws_limit / 16));
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        CH = std::max<uint64_t>(1u << 16, std::min<uint64_t>(CH, (fr + held_bytes(c, BUF_WORK)) / 32));
+    }
+    CH = std::max<uint64_t>(16, std::min<uint64_t>(CH, std::max<uint64_t>(R.n_words, 16)));
+    struct Scratch { mtb_ctx *c; ~Scratch() { for (const char *nm : {"auditv", "auditi", "auditbins", "auditlisted", "auditout", "auditcp", "diffraw", "difftc", "difftoff"}) release(c, nm); } } scratch{c};
+    uint64_t *d_v; uint32_t *d_i, *d_bins; uint8_t *d_listed; unsigned long long *d_out; mtb_audit_checkpoint *d_cp;
+    const uint32_t CP_MAX = 4096;                                  /* checkpoints judged per launch */
+    STCHK(ensure(c, "auditv", CH + 16, &d_v)); STCHK(ensure(c, "auditi", CH + 16, &d_i));
+    /* how the counts are taken: in the check kernel, a hot species folded in the wave, one bin array per XCD summed at the end -- or,
+     * for measurements (mtb_debug_audit_mode): 1 not at all, 2 one add per entry, 3 / 4 as 0 / 2 into a single bin array */
+    const int mode = c->audit_mode;
+    const bool replicated = mode == 0 || mode == 2;
+    const int fold_rounds = mode == 2 || mode == 4 ? 0 : MTB_AUDIT_FOLD_ROUNDS;
+    const uint64_t bin_stride = replicated ? ((n_bins + 63) & ~63ull) : 0, bin_words = replicated ? bin_stride * MTB_AUDIT_REPLICAS : n_bins;
+    STCHK(ensure(c, "auditbins", bin_words, &d_bins)); STCHK(ensure(c, "auditlisted", n_bins + 1, &d_listed));
+    STCHK(ensure(c, "auditout", (size_t)MTB_AUDIT_WORDS + 4, &d_out)); STCHK(ensure(c, "auditcp", (size_t)CP_MAX, &d_cp));
+    uint64_t *d_prev = (uint64_t *)(d_out + MTB_AUDIT_WORDS);      /* two {value, species} pairs, used in turn */
+    {   /* counters 0, first positions ~0; the listed ids as the byte map of k_mark_taxids */
+        unsigned long long init[MTB_AUDIT_WORDS + 4];
+        for (int k = 0; k < MTB_AUDIT_WORDS + 4; k++) init[k] = 0;
+        for (int k = 0; k < MTB_AUDIT_COUNTERS; k++) init[MTB_AUDIT_FIRST + k] = ~0ull;
+        init[MTB_AUDIT_FIRST_BAD_CP] = ~0ull;
+        STCHK(h2d(c, d_out, init, sizeof(init)));
+        std::vector<uint8_t> listed(n_bins + 1, 0);
+        for (int32_t t : ids) if (t >= 0 && (uint64_t)t < n_bins) listed[(size_t)t] = 1;
+        STCHK(h2d(c, d_listed, listed.data(), listed.size())); }
+    float ms_hist = 0;
+    {   const auto t0 = std::chrono::steady_clock::now();
+        HIPCHK(hipMemsetAsync(d_bins, 0, bin_words * 4, st)); HIPCHK(hipStreamSynchronize(st));
+        ms_hist += (float)ms_since(t0); }
+    ChunkSink sink;
+    struct Events { hipEvent_t *e; ~Events() { for (int k = 0; k < 3; k++) if (e[k]) { hipError_t x = hipEventDestroy(e[k]); (void)x; } } } events{sink.ev};
+    for (int k = 0; k < 3; k++) HIPCHK(hipEventCreate(&sink.ev[k]));
+    sink.chunk_words = CH;
+    size_t next_cp = 0; uint64_t missed_cp = 0, first_missed_cp = UINT64_MAX; int turn = 0;
+    std::vector<mtbhost::AuditCheckpoint> take; std::vector<mtb_audit_checkpoint> rel;
+    sink.on_chunk = [&](const DecodedChunk &k) -> mtb_status {
+        if (k.n_info) {
+            const uint64_t blocks = (k.n_info + 256ull * MTB_AUDIT_PER_LANE - 1) / (256ull * MTB_AUDIT_PER_LANE);
+            hipLaunchKernelGGL(k_audit_order, dim3((uint32_t)std::min<uint64_t>(blocks, 1u << 16)), dim3(256), 0, st, k.d_values, k.d_info, k.n_info, k.first_entry, hold->info_mask, tv,
+                               (const int32_t *)hold->d_tax2species, (const uint8_t *)d_listed, (const uint64_t *)(d_prev + 2 * turn), d_prev + 2 * (turn ^ 1), d_out, mode == 1 ? (uint32_t *)nullptr : d_bins, fold_rounds, bin_stride);
+            turn ^= 1;
+        }
+        mtbhost::audit_chunk_checkpoints(cps, &next_cp, k.word0, k.n_words, &take, &missed_cp, &first_missed_cp);
+        for (size_t at = 0; at < take.size(); at += CP_MAX) {
+            const uint32_t n = (uint32_t)std::min<size_t>(CP_MAX, take.size() - at);
+            rel.resize(n);
+            for (uint32_t q = 0; q < n; q++) {
+                const mtbhost::AuditCheckpoint &a = take[at + q];
+                rel[q].ad = a.cp.ad; rel[q].diff_off = a.cp.diff_off - k.word0; rel[q].info_off = a.cp.info_off - k.first_entry; rel[q].record = a.record;       /* (an info_off before the chunk wraps: never equal to a count) */
+            }
+            STCHK(h2d(c, d_cp, rel.data(), (size_t)n * sizeof(mtb_audit_checkpoint)));
+            hipLaunchKernelGGL(k_audit_checkpoints, dim3((n + 63) / 64), dim3(64), 0, st, k.d_words, k.n_words, k.d_tile_off, k.d_values, k.n_values, (const mtb_audit_checkpoint *)d_cp, n, d_out);
+        }
+        HIPCHK(hipGetLastError());
+        return MTB_OK;
+    };
+    {   mtb_index tmp; tmp.ctx = c; tmp.params = *params; tmp.d_values = d_v; tmp.d_info = d_i;
+        OpenPlan P; P.n16 = R.n_words - R.n_trailing_words; P.T = R.n_info_entries; P.expect = UINT64_MAX;
+        bool dir_ok = false;
+        const mtb_status s = decode_chunked(c, &tmp, d, P, false, 1, false, &dir_ok, &sink);
+        if (s != MTB_OK) return failed(s); }
+    /* checkpoints behind the last decoded word (among the trailing words) were never offered to a chunk */
+    for (; next_cp < cps.size(); next_cp++) { missed_cp++; first_missed_cp = std::min(first_missed_cp, cps[next_cp].record); }
+    unsigned long long h[MTB_AUDIT_WORDS];
+    STCHK(d2h(c, h, d_out, sizeof(h)));
+    R.n_end_words = sink.n_entries; R.n_entries = std::min(R.n_end_words, R.n_info_entries); R.n_chunks = sink.n_chunks;
+    R.n_value_descents = h[MTB_AUDIT_DESCENT]; R.first_value_descent = h[MTB_AUDIT_FIRST + MTB_AUDIT_DESCENT];
+    R.n_group_disorder = h[MTB_AUDIT_DISORDER]; R.first_group_disorder = h[MTB_AUDIT_FIRST + MTB_AUDIT_DISORDER];
+    R.n_unknown_ids = h[MTB_AUDIT_UNKNOWN]; R.first_unknown_id = h[MTB_AUDIT_FIRST + MTB_AUDIT_UNKNOWN];
+    R.n_unlisted_ids = h[MTB_AUDIT_UNLISTED]; R.first_unlisted_id = h[MTB_AUDIT_FIRST + MTB_AUDIT_UNLISTED];
+    R.n_no_species = h[MTB_AUDIT_NO_SPECIES];
+    R.n_bad_checkpoints = h[MTB_AUDIT_BAD_CP] + missed_cp; R.first_bad_checkpoint = std::min<uint64_t>(h[MTB_AUDIT_FIRST_BAD_CP], first_missed_cp);
+    {   const auto t0 = std::chrono::steady_clock::now();
+        std::vector<uint32_t> own;
+        uint32_t *bins = species_counts;
+        if (!bins) { own.resize(n_bins); bins = own.data(); }
+        if (replicated) { hipLaunchKernelGGL(k_audit_bins_reduce, grid256(n_bins), dim3(256), 0, st, d_bins, n_bins, bin_stride); HIPCHK(hipGetLastError()); }
+        STCHK(d2h(c, bins, d_bins, n_bins * 4));
+        for (uint64_t s = 0; s < n_bins; s++) if (bins[s]) R.n_species++;
+        ms_hist += (float)ms_since(t0); }
+    R.valid = R.n_end_words == R.n_info_entries && !R.n_trailing_words && !R.n_value_descents && !R.n_unknown_ids && !R.n_bad_checkpoints;
+    R.canonical = R.valid && !R.n_group_disorder && !R.n_unlisted_ids;
+    R.ms_read = (float)sink.us_read.load() / 1000.0f; R.ms_decode = sink.ms_decode; R.ms_check = sink.ms_sink; R.ms_hist = ms_hist;
+    R.ms_total = (float)ms_since(t_all);
+    *out = R;
+    return MTB_OK;
+}
+
+/* measurements only (profiles/scripts/audit_measure.py; not declared in mtb.h): see mtb_database_audit */
+mtb_status mtb_debug_audit_mode(mtb_ctx *c, int mode) {
+    if (!c || mode < 0 || mode > 4) return fail(MTB_ERR_ARG, "audit mode 0..4");
+    c->audit_mode = mode;
+    return MTB_OK;
+}
+
+mtb_status mtb_audit_write_species_counts(const char *dbdir, const uint32_t *species_counts, uint64_t n) {
+    if (!dbdir || (!species_counts && n)) return fail(MTB_ERR_ARG, "NULL argument");
+    const std::string path = std::string(dbdir) + "/sp2uniqKmerCnt";
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) return fail(MTB_ERR_IO, "cannot create " + path);
+    for (uint64_t s = 0; s < n; s++) if (species_counts[s]) fprintf(f, "%llu %u\n", (unsigned long long)s, species_counts[s]);
+    if (fclose(f) != 0) return fail(MTB_ERR_IO, "short write to " + path);
     return MTB_OK;
 }
 
