@@ -120,6 +120,12 @@ inline std::vector<std::string> split_dmp(const std::string &line) {
 /* one node as either source delivers it */
 struct RawNode { int32_t id, parent; std::string rank, name; };
 
+/* the tables are dense in the taxon id (NCBI ids are below 2^22 today): a damaged file must not ask for tens of GB of them */
+inline bool plausible_max_taxid(int32_t mx, std::string *err) {
+    if (mx > (1 << 28)) { *err = "taxonomy: implausible taxon id " + std::to_string(mx); return false; }
+    return true;
+}
+
 /* Dense arrays from a node list: `aliases` = (old id, current id) pairs (merged.dmp / the D table of taxonomyDB),
  * `eukaryota` = id of the node named "Eukaryota" (0 if none; setEukaryoteTaxID, TaxonomyWrapper.h:89-100),
  * `orig` = internal -> original id (getOriginalTaxID, TaxonomyWrapper.h:70-79), empty = identity. */
@@ -128,8 +134,7 @@ inline bool finalize_taxonomy(Taxonomy *t, const std::vector<RawNode> &nodes, co
     int32_t mx = std::max<int32_t>(max_id, 1);
     for (auto &n : nodes) mx = std::max(mx, std::max(n.id, n.parent));
     for (auto &m : aliases) mx = std::max(mx, std::max(m.first, m.second));
-    /* the tables are dense in the taxon id (NCBI ids are below 2^22 today): a damaged file must not ask for tens of GB of them */
-    if (mx > (1 << 28)) { *err = "taxonomy: implausible taxon id " + std::to_string(mx); return false; }
+    if (!plausible_max_taxid(mx, err)) return false;
     t->max_id = mx;
     size_t sz = (size_t)mx + 1;
     t->canon.assign(sz, -1); t->parent.assign(sz, -1); t->depth.assign(sz, 0); t->rank_idx.assign(sz, -1);
@@ -194,6 +199,7 @@ inline bool load_taxonomy(const std::string &dir, Taxonomy *t, std::string *err)
             mx = std::max(mx, std::max(merged.back().first, merged.back().second));
         }
     }
+    if (!plausible_max_taxid(mx, err)) return false;          /* before the first table sized by it */
     int32_t eukaryota = 0;
     {
         std::vector<int32_t> slot((size_t)mx + 1, -1);

@@ -360,6 +360,51 @@ def tax2species_table(orc: Oracle, tax, taxids, mx):
     return tab
 
 
+def part_stages(ctx, index, params):
+    """metabuli_amd.parallel.GpuStages over libmtb's mtb_part_* calls, and the torch device its tensors live on.  On a GPU that is the
+    product class with device tensors.  Under MTB_HIPEMU (the emulated build of tests/hipemu) "device" memory is host memory: CPU
+    tensors, nothing to fence, and the context-owned sorted list seen through numpy."""
+    import torch
+    from metabuli_amd import parallel
+    if not os.environ.get("MTB_HIPEMU"):
+        dev = torch.device("cuda:0")
+        return parallel.GpuStages(ctx, index, params, dev), dev
+
+    class Stages(parallel.GpuStages):
+        def _fence(self):
+            pass
+
+        def extract_sorted(self, bounds):
+            b, o, b2, o2 = self.reads
+            ptr, nk, counts, starts = self.ctx.part_extract(self.params, b.data_ptr(), o.data_ptr(), b2.data_ptr() if b2 is not None else 0,
+                                                            o2.data_ptr() if o2 is not None else 0, self.n_reads, bounds, overlapping=self.overlapping)
+            if nk == 0:
+                return torch.empty((0, 2), dtype=torch.int64), [0] * len(counts), [0] * len(counts)
+            view = np.ctypeslib.as_array((C.c_int64 * (2 * int(nk))).from_address(int(ptr))).reshape(int(nk), 2)
+            return torch.from_numpy(view), [int(c) for c in counts], [int(x) for x in starts]
+    dev = torch.device("cpu")
+    return Stages(ctx, index, params, dev), dev
+
+
+def part_extract_records(ctx, params, b1, o1, b2=None, o2=None):
+    """mtb_part_extract with one partition (bounds = [0]) and part_starts given: dev_extract's tagged single pass with digits, then
+    dev_sort on the leading amino-acid letters -- the sorted list, blank records included, as a host copy (kmer_dt)"""
+    import torch
+    st, dev = part_stages(ctx, None, params)
+
+    def up(a, dt):
+        a = np.ascontiguousarray(a).astype(dt)
+        return torch.from_numpy(a if len(a) else np.zeros(1, dt)).to(dev)
+    n = len(o1) - 1
+    if b2 is None:
+        st.set_reads(up(b1, np.uint8), up(o1, np.int64), n)
+    else:
+        st.set_reads(up(b1, np.uint8), up(o1, np.int64), n, up(b2, np.uint8), up(o2, np.int64))
+    kt, counts, starts = st.extract_sorted(np.zeros(1, np.uint64))
+    assert counts == [int(kt.shape[0])] and starts == [0], (counts, starts, kt.shape)
+    return kt.cpu().numpy().copy().view(np.uint64).reshape(-1).view(kmer_dt)
+
+
 def build_toy_db(orc: Oracle, world, p, dbdir, extra=None):
     """Extract target metamers of every genome with the oracle scanners, dedup
     per (value, species), optionally merge `extra` = (values, taxids), write the

@@ -113,6 +113,14 @@ def test_join_past_the_last_target_on_the_emulator(emulated_lib):
     _run(emulated_lib, "test_fused_join_at_the_ends_of_the_index and sync_se and head15 and (window_qt256 or q1w6)", module="test_gpu_join_edges.py")
 
 
+def test_single_pass_records_and_the_overflow_retry_on_the_emulator(emulated_lib):
+    """what the single-pass extractor and the fused sort write, record by record (tests/test_gpu_extract_records.py, through mtb_part_extract):
+    dense reads of every window count up to the slot limit, the 320-base staging edge with s = 5, pairs, a read that fills the LDS buffer
+    exactly; and dev_extract's second launch at the bound after an overflow.  (The 70 000-read batch and the tile-edge sorts stay with the GPU.)"""
+    _run(emulated_lib, "(test_single_pass_records and (dense-fmt2 or sync5-staging-edge or pairs)) or test_buffer_flush_at_its_capacity "
+                       "or test_overflow_retry_through_the_fused_batch", module="test_gpu_extract_records.py")
+
+
 def test_bench_line_of_two_ranks_on_the_emulator(emulated_lib, tmp_path):
     """bench.py's main() launched the way the driver launches bench.py for N = 2 (torch.distributed.run, one rank per GPU; here gloo and the
     emulated build, through tests/hipemu/bench_emulated.py, which hands main() a CPU device): every rank classifies its own reads against its own replica, the time is the maximum over the ranks, rank 0 prints ONE
