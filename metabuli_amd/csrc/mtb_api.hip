@@ -1210,6 +1210,9 @@ static mtb_status count_reads(mtb_ctx *c, const mtb_match *d_in, uint64_t n, uin
     return MTB_OK;
 }
 
+/* info entries of a database written without Skip_redundancy carry a flag in bit 31 (KmerMatcher.cpp:204-205, IndexCreator.h:355, 400) */
+static uint32_t legacy_info_mask(int skip_redundancy) { return ~((uint32_t)(skip_redundancy == 0) << 31); }
+
 static mtb_status upload_taxonomy(mtb_index *ix) {
     const mtbhost::Taxonomy &t = ix->tax;
     size_t n = (size_t)t.max_id + 1;
@@ -1236,6 +1239,19 @@ static mtb_status upload_taxonomy(mtb_index *ix) {
         HIPCHK(hipMalloc((void **)&ix->d_node, n * sizeof(mtb_tax_node)));
         HIPCHK(hipMemcpy(ix->d_node, nodes.data(), n * sizeof(mtb_tax_node), hipMemcpyHostToDevice));
     }
+    return MTB_OK;
+}
+
+/* A taxonomy and its species table on the device without targets: what the merge and the audit look ids up in.  `tax` is the loaded
+ * taxonomy, `ids` the ids the species table is built from (as for a database's taxID_list at index open). */
+static mtb_status tax_holder_index(mtb_ctx *c, const mtb_params &params, mtbhost::Taxonomy &&tax, const std::vector<int32_t> &ids, mtb_index **out) {
+    mtb_index *hold = new mtb_index();
+    hold->ctx = c; hold->params = params; hold->own = true; hold->info_mask = legacy_info_mask(params.skip_redundancy);
+    hold->tax = std::move(tax);
+    mtbhost::build_tax2species(&hold->tax, ids.data(), ids.size());
+    const mtb_status st = upload_taxonomy(hold);
+    if (st != MTB_OK) { mtb_index_close(hold); return st; }
+    *out = hold;
     return MTB_OK;
 }
 
@@ -1275,55 +1291,29 @@ static mtb_dir_view dir_view(const mtb_index *ix) {
 }
 /* the two states of the target array: flat {value[T], info[T]} (every stage-level entry point, download / write / slices) and packed
  * (the fused join; depth-7 directory only).  Conversions are in place, ~25 ms each at 16 G targets, and happen only on a change of use. */
-/* How a database directory is cut into n_parts value ranges at `split` checkpoints (IndexCreator.cpp:848-857: a
- * checkpoint {value, diffIdx offset after it, info index + 1} sits on the first metamer of an amino-acid group).  */
-struct PartPlan {
-    struct P { bool empty = true, explicit_first = false, drop_last = false; uint64_t ad = 0, diff_lo = 0, diff_hi = 0, info_lo = 0, info_hi = 0; };
-    std::vector<P> parts;
-    std::vector<uint64_t> bounds;       /* lower amino-acid-part bound of every partition */
-};
-static mtb_status plan_parts(const std::string &d, uint32_t n_parts, PartPlan *plan) {
-    struct Split { uint64_t ad, diff_off, info_off; };
-    std::vector<Split> sp;
+/* The partitions of a database directory (host/merge_plan.h: plan_parts) from its file sizes and, for more than one, its `split` table */
+static mtb_status plan_parts(const std::string &d, uint32_t n_parts, mtbhost::PartPlan *plan) {
     FILE *f = fopen((d + "/diffIdx").c_str(), "rb"); if (!f) return fail(MTB_ERR_IO, "cannot open " + d + "/diffIdx");
     fseek(f, 0, SEEK_END); const uint64_t n16 = (uint64_t)ftell(f) / 2; fclose(f);
     f = fopen((d + "/info").c_str(), "rb"); if (!f) return fail(MTB_ERR_IO, "cannot open " + d + "/info");
     fseek(f, 0, SEEK_END); const uint64_t T = (uint64_t)ftell(f) / 4; fclose(f);
-    std::vector<Split> use; use.push_back(Split{0, 0, 0});
-    if (n_parts > 1) {
-        if (!mtbhost::read_whole(d + "/split", &sp)) return fail(MTB_ERR_IO, "cannot read " + d + "/split");
-        for (size_t i = 1; i < sp.size(); i++) if (sp[i].ad != 0 && sp[i].ad != UINT64_MAX && sp[i].info_off > use.back().info_off) use.push_back(sp[i]);
-    }
-    plan->parts.assign(n_parts, PartPlan::P()); plan->bounds.assign(n_parts, UINT64_MAX);
-    const size_t U = use.size();
-    std::vector<size_t> k(n_parts + 1);
-    for (uint32_t p = 0; p <= n_parts; p++) k[p] = (size_t)((uint64_t)p * U / n_parts);
-    for (uint32_t p = 0; p < n_parts; p++) {
-        PartPlan::P &P = plan->parts[p];
-        if (k[p] == k[p + 1] || T == 0) continue;
-        P.empty = false;
-        const Split &s0 = use[k[p]];
-        if (k[p] == 0) { P.explicit_first = false; P.ad = 0; P.diff_lo = 0; P.info_lo = 0; }
-        else { P.explicit_first = true; P.ad = s0.ad; P.diff_lo = s0.diff_off; P.info_lo = s0.info_off - 1; }
-        if (k[p + 1] >= U) { P.drop_last = false; P.diff_hi = n16; P.info_hi = T; }
-        else { P.drop_last = true; P.diff_hi = use[k[p + 1]].diff_off; P.info_hi = use[k[p + 1]].info_off - 1; }
-        plan->bounds[p] = k[p] == 0 ? 0 : (s0.ad & ~0xFFFFFFull);
-    }
-    for (int64_t p = (int64_t)n_parts - 2; p >= 0; p--) if (plan->parts[(size_t)p].empty) plan->bounds[(size_t)p] = plan->bounds[(size_t)p + 1];
-    if (T == 0) plan->bounds[0] = 0;
+    std::vector<mtbhost::MergeCheckpoint> sp;
+    if (n_parts > 1 && !mtbhost::read_whole(d + "/split", &sp)) return fail(MTB_ERR_IO, "cannot read " + d + "/split");
+    mtbhost::plan_parts(sp, T, n16, n_parts, plan);
     return MTB_OK;
 }
 
-/* bytes [off, off + len) of a file into a (pinned) host buffer, with a few threads: one pread stream tops out near 3 GB/s from the page
- * cache, the files of a GTDB-scale database are ~150 GB */
-static bool pread_parallel(int fd, void *dst, uint64_t off, size_t len, int n_threads) {
+/* bytes [off, off + len) of a file from / into a (pinned) host buffer, with a few threads: one pread stream tops out near 3 GB/s from
+ * the page cache, the files of a GTDB-scale database are ~150 GB */
+template <typename Op>
+static bool pio_parallel(Op op, int fd, char *buf, uint64_t off, size_t len, int n_threads) {
     if (len == 0) return true;
     const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_threads, len >> 22));
     std::vector<char> ok((size_t)nt, 1);
     auto part = [&](int t) {
         size_t lo = len * (size_t)t / (size_t)nt, hi = len * ((size_t)t + 1) / (size_t)nt;
         while (lo < hi) {
-            const ssize_t r = pread(fd, (char *)dst + lo, hi - lo, (off_t)(off + lo));
+            const ssize_t r = op(fd, buf + lo, hi - lo, (off_t)(off + lo));
             if (r <= 0) { ok[(size_t)t] = 0; return; }
             lo += (size_t)r;
         }
@@ -1333,50 +1323,8 @@ static bool pread_parallel(int fd, void *dst, uint64_t off, size_t len, int n_th
     for (char k : ok) if (!k) return false;
     return true;
 }
-
-static bool pwrite_parallel(int fd, const void *src, uint64_t off, size_t len, int n_threads) {
-    if (len == 0) return true;
-    const int nt = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_threads, len >> 22));
-    std::vector<char> ok((size_t)nt, 1);
-    auto part = [&](int t) {
-        size_t lo = len * (size_t)t / (size_t)nt, hi = len * ((size_t)t + 1) / (size_t)nt;
-        while (lo < hi) {
-            const ssize_t r = pwrite(fd, (const char *)src + lo, hi - lo, (off_t)(off + lo));
-            if (r <= 0) { ok[(size_t)t] = 0; return; }
-            lo += (size_t)r;
-        }
-    };
-    if (nt == 1) part(0);
-    else { std::vector<std::thread> th; for (int t = 0; t < nt; t++) th.emplace_back(part, t); for (auto &x : th) x.join(); }
-    for (char k : ok) if (!k) return false;
-    return true;
-}
-
-/* bytes [off, off + len) of a file -> device memory, double-buffered through pinned host memory */
-static mtb_status stream_file_to_device(mtb_ctx *c, const std::string &path, uint64_t off, uint64_t len, void *d_dst) {
-    if (len == 0) return MTB_OK;
-    const int fd = open(path.c_str(), O_RDONLY);
-    if (fd < 0) return fail(MTB_ERR_IO, "cannot open " + path);
-    const size_t CH = 64u << 20;
-    void *buf[2] = {nullptr, nullptr}; hipEvent_t ev[2] = {nullptr, nullptr}; bool used[2] = {false, false};
-    mtb_status st = MTB_OK;
-    if (hipHostMalloc(&buf[0], CH, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&buf[1], CH, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) { (void)hipGetLastError(); st = fail(MTB_ERR_OOM, "no pinned host memory for the index upload"); }
-    uint64_t done = 0; int k = 0;
-    while (st == MTB_OK && done < len) {
-        const size_t n = (size_t)std::min<uint64_t>(CH, len - done);
-        if (used[k] && hipEventSynchronize(ev[k]) != hipSuccess) { st = fail(MTB_ERR_DEVICE, "hipEventSynchronize failed during the index upload"); break; }
-        if (!pread_parallel(fd, buf[k], off + done, n, 8)) { st = fail(MTB_ERR_IO, "short read from " + path); break; }
-        if (hipMemcpyAsync((char *)d_dst + done, buf[k], n, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipEventRecord(ev[k], c->stream) != hipSuccess) {
-            st = fail(MTB_ERR_DEVICE, "H2D copy failed during the index upload"); break; }
-        used[k] = true; done += n; k ^= 1;
-    }
-    hipError_t e = hipStreamSynchronize(c->stream); (void)e;
-    close(fd);
-    for (int i = 0; i < 2; i++) { if (buf[i]) e = hipHostFree(buf[i]); if (ev[i]) e = hipEventDestroy(ev[i]); }
-    (void)e;
-    return st;
-}
+static bool pread_parallel(int fd, void *dst, uint64_t off, size_t len, int n_threads) { return pio_parallel(pread, fd, (char *)dst, off, len, n_threads); }
+static bool pwrite_parallel(int fd, const void *src, uint64_t off, size_t len, int n_threads) { return pio_parallel(pwrite, fd, (char *)src, off, len, n_threads); }
 
 /* The target list of a database (or of one value range of it) into HBM, decoded in CHUNKS of the diffIdx stream (the reference streams
  * the files too: KmerMatcher.cpp:212-217, 256-271, getNextTargetKmer KmerMatcher.h:282-297):
@@ -1386,15 +1334,24 @@ static mtb_status stream_file_to_device(mtb_ctx *c, const std::string &path, uin
  *   buffer) are folded into packed 8-byte words at once (kernels_dir.h) and info[] is never resident.
  * Peak HBM: 8 bytes per target (+ 4 for info[] without `pack`) + the directory + one chunk (2 B per word, 4 B per metamer of it):
  * a 16 G-target database opens on one 288 GB GPU; the whole-file decode of round 3 held ~18 bytes per target at once.
- * On return *dir_ok says whether the directory is usable (else it has been freed); with `pack` a false *dir_ok is an error to the
+ * What is decoded is a range of the files (host/merge_plan.h: MergeSlice), into value[R.records() + 1] and info[R.records()].
+ * Only an open asks for more: the directory (and with `pack` the packed state) of the index the arrays belong to, and its statistics.
+ * On return dir_ok says whether the directory is usable (else it has been freed); with `pack` a false dir_ok is an error to the
  * caller (the array is partly packed): it opens again without. */
-struct OpenPlan { uint64_t n16 = 0, T = 0, expect = 0, lead = 0, diff_off = 0, info_off = 0, first_value = 0; };
-/* A caller that looks at every decoded chunk instead of keeping the array (mtb_database_audit): with a sink, value[] and info[] of the
- * index are CHUNK buffers (chunk_words + 9 values, as many info entries) that every chunk overwrites, the number of entries is
- * whatever the words hold (P.expect is not consulted; info entries are read while the file has them: P.T) and on_chunk runs on
+/* 16-bit words per chunk: 128 M (256 MB), less when the context's workspace limit asks for it (a chunk costs ~16 bytes per word: the
+ * words twice, tile tables, the info entries of its metamers, scan workspace) */
+static uint64_t decode_chunk_words(const mtb_ctx *c) { return c->ws_limit ? std::max<uint64_t>(1u << 16, std::min<uint64_t>(128ull << 20, c->ws_limit / 16)) : 128ull << 20; }
+struct OpenDirectory { mtb_index *ix = nullptr; bool want_dir = false; int L = 1; bool pack = false, dir_ok = false; };
+/* the decode's chunk buffers in the context's workspace.  A caller declares one DecodeScratch around its decodes (not one per
+ * decode: the merge decodes once per slice): they go back when it leaves the scope, whatever way the decodes ended */
+static const char *const DECODE_WORDS = "diffraw", *const DECODE_TILE_COUNT = "difftc", *const DECODE_TILE_OFF = "difftoff", *const DECODE_INFO = "infochunk";
+struct DecodeScratch { mtb_ctx *c; ~DecodeScratch() { for (const char *nm : {DECODE_WORDS, DECODE_TILE_COUNT, DECODE_TILE_OFF, DECODE_INFO}) release(c, nm); } };
+/* A caller that looks at every decoded chunk instead of keeping the array (mtb_database_audit): with a sink, value[] and info[]
+ * are CHUNK buffers (chunk_words + 9 values, as many info entries) that every chunk overwrites, the number of entries is
+ * whatever the words hold (R.coded_entries() is not consulted; info entries are read while the file has them: R.records()) and on_chunk runs on
  * the stream behind each chunk's decode, before the buffers are reused. */
 struct DecodedChunk {
-    const uint16_t *d_words; uint64_t n_words, word0;      /* the chunk's words and the file offset (in words, from P.diff_off) of the first */
+    const uint16_t *d_words; uint64_t n_words, word0;      /* the chunk's words and the file offset (in words, from R.diff_lo) of the first */
     const uint64_t *d_tile_off;                            /* end words before each 2048-word tile of the chunk (and, last, all of them) */
     const uint64_t *d_values; uint64_t n_values;           /* entries first_entry .. first_entry + n_values */
     const uint32_t *d_info; uint64_t n_info;               /* info entries of the first n_info of them */
@@ -1408,13 +1365,12 @@ struct ChunkSink {
     std::atomic<uint64_t> us_read{0};                      /* host clock inside the file reads (they overlap the device) */
     float ms_decode = 0, ms_sink = 0;
 };
-static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d, const OpenPlan &P, bool want_dir, int L, bool pack, bool *dir_ok, ChunkSink *sink = nullptr) {
-    *dir_ok = false;
+static mtb_status decode_chunked(mtb_ctx *c, int fmt, const std::string &d, const mtbhost::MergeSlice &R, uint64_t *d_values, uint32_t *d_info, OpenDirectory *dir = nullptr, ChunkSink *sink = nullptr) {
+    mtb_index *ix = dir ? dir->ix : nullptr;
+    const bool want_dir = dir && dir->want_dir, pack = dir && dir->pack; const int L = dir ? dir->L : 1;
+    const uint64_t T = R.records();
     hipStream_t st = c->stream;
-    /* 16-bit words per chunk: 128 M (256 MB), less when the context's workspace limit asks for it (a chunk costs ~16 bytes per word:
-     * the words twice, tile tables, the info entries of its metamers, scan workspace); MTB_OPEN_CHUNK: tests (a few dozen words) */
-    uint64_t CH = 128ull << 20;
-    if (c->ws_limit) CH = std::max<uint64_t>(1u << 16, std::min<uint64_t>(CH, c->ws_limit / 16));
+    uint64_t CH = decode_chunk_words(c);                   /* MTB_OPEN_CHUNK: tests (a few dozen words) */
     if (c->opt.open_chunk > 0) CH = std::max<uint64_t>(16, (uint64_t)c->opt.open_chunk);
     if (sink && sink->chunk_words) CH = std::max<uint64_t>(16, sink->chunk_words);
     auto timed_read = [sink](int fd, void *dst, uint64_t off, size_t len, int n_threads) {
@@ -1423,7 +1379,6 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
         if (sink) sink->us_read += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
         return ok;
     };
-    const int fmt = ix->params.kmer_format;
     const uint32_t nbk = want_dir ? mtb_pow21(L) : 0, n_groups = want_dir ? (nbk >> 16) + 1 : 0;
     uint32_t *d_flags = scal<uint32_t>(c, SC_OPEN_FLAGS);
     uint64_t *d_carry = scal<uint64_t>(c, SC_OPEN_CARRY);                      /* last flat value of the previous chunk */
@@ -1435,44 +1390,44 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
     const int fd_d = open((d + "/diffIdx").c_str(), O_RDONLY), fd_i = open((d + "/info").c_str(), O_RDONLY);
     struct Files { int a, b; ~Files() { if (a >= 0) close(a); if (b >= 0) close(b); } } files{fd_d, fd_i};
     if (fd_d < 0 || fd_i < 0) return fail(MTB_ERR_IO, "cannot open diffIdx / info in " + d);
-    const uint64_t chunk_words = std::min<uint64_t>(CH, std::max<uint64_t>(P.n16, 1));
-    const uint64_t info_cap = std::min<uint64_t>(chunk_words + 8, P.T + 1);      /* metamers of a chunk <= its words */
+    const uint64_t chunk_words = std::min<uint64_t>(CH, std::max<uint64_t>(R.words(), 1));
+    const uint64_t info_cap = std::min<uint64_t>(chunk_words + 8, T + 1);      /* metamers of a chunk <= its words */
     struct Pinned { void *p[3] = {nullptr, nullptr, nullptr}; ~Pinned() { for (void *q : p) if (q) { hipError_t e = hipHostFree(q); (void)e; } } } pin;
     if (hipHostMalloc(&pin.p[0], (chunk_words + 8) * 2, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&pin.p[1], (chunk_words + 8) * 2, hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(&pin.p[2], info_cap * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(MTB_ERR_OOM, "no pinned host memory for the index upload"); }
     uint16_t *d_chunk; uint32_t *d_tc; uint64_t *d_toff, *d_ws; uint32_t *d_ichunk = nullptr;
     const uint64_t max_tiles = (chunk_words + 8 + 2047) / 2048 + 1;
-    STCHK(ensure(c, "diffraw", chunk_words + 8, &d_chunk)); STCHK(ensure(c, "difftc", max_tiles, &d_tc)); STCHK(ensure(c, "difftoff", max_tiles + 1, &d_toff));
+    STCHK(ensure(c, DECODE_WORDS, chunk_words + 8, &d_chunk)); STCHK(ensure(c, DECODE_TILE_COUNT, max_tiles, &d_tc)); STCHK(ensure(c, DECODE_TILE_OFF, max_tiles + 1, &d_toff));
     STCHK(ensure(c, "scanws", scan_ws_elems(std::max<uint64_t>(max_tiles + 1, info_cap + 1)), &d_ws));
-    if (pack) STCHK(ensure(c, "infochunk", info_cap, &d_ichunk));
-    { const uint64_t c0 = P.lead ? P.first_value : 0; STCHK(h2d(c, d_carry, &c0, 8)); }
-    if (P.lead) {
+    if (pack) STCHK(ensure(c, DECODE_INFO, info_cap, &d_ichunk));
+    { const uint64_t c0 = R.lead ? R.first_value : 0; STCHK(h2d(c, d_carry, &c0, 8)); }
+    if (R.lead) {
         /* a range that starts at a split checkpoint: its first metamer is given by the checkpoint, not coded in the byte range -- a chunk
          * of one entry (value, info entry, directory rows, packing) */
-        STCHK(h2d(c, ix->d_values, &P.first_value, 8));
-        if (!pread_parallel(fd_i, pin.p[2], P.info_off * 4, 4, 1)) return fail(MTB_ERR_IO, "short read from " + d + "/info");
-        STCHK(h2d(c, pack ? d_ichunk : ix->d_info, pin.p[2], 4));
+        STCHK(h2d(c, d_values, &R.first_value, 8));
+        if (!pread_parallel(fd_i, pin.p[2], R.info_lo * 4, 4, 1)) return fail(MTB_ERR_IO, "short read from " + d + "/info");
+        STCHK(h2d(c, pack ? d_ichunk : d_info, pin.p[2], 4));
         if (want_dir) {
-            hipLaunchKernelGGL(k_dir_chunk_base, dim3(1), dim3(256), 0, st, (const uint64_t *)ix->d_values, (uint64_t)0, (uint64_t)1, (const uint64_t *)d_carry, L, fmt, nbk, ix->d_dirbase, d_flags);
-            hipLaunchKernelGGL(k_dir_chunk_fill, dim3(1), dim3(256), 0, st, (const uint64_t *)ix->d_values, (uint64_t)0, (uint64_t)1, (const uint64_t *)d_carry, L, fmt, nbk,
+            hipLaunchKernelGGL(k_dir_chunk_base, dim3(1), dim3(256), 0, st, (const uint64_t *)d_values, (uint64_t)0, (uint64_t)1, (const uint64_t *)d_carry, L, fmt, nbk, ix->d_dirbase, d_flags);
+            hipLaunchKernelGGL(k_dir_chunk_fill, dim3(1), dim3(256), 0, st, (const uint64_t *)d_values, (uint64_t)0, (uint64_t)1, (const uint64_t *)d_carry, L, fmt, nbk,
                                (const uint64_t *)ix->d_dirbase, ix->d_dir, d_flags);
         }
-        if (pack) hipLaunchKernelGGL(k_index_pack_chunk, dim3(1), dim3(256), 0, st, ix->d_values, (const uint32_t *)d_ichunk, (uint64_t)0, (uint64_t)1, fmt);
+        if (pack) hipLaunchKernelGGL(k_index_pack_chunk, dim3(1), dim3(256), 0, st, d_values, (const uint32_t *)d_ichunk, (uint64_t)0, (uint64_t)1, fmt);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
     }
-    ix->open_chunk_words = chunk_words;
-    uint64_t done_words = 0, g = P.lead, found = 0;       /* g: next free place in value[] */
+    if (ix) ix->open_chunk_words = chunk_words;
+    uint64_t done_words = 0, g = R.lead, found = 0;       /* g: next free place in value[] */
     uint16_t carry_w[8]; uint32_t n_carry = 0;
     /* the first chunk is read here, every further one by a helper thread while the device works on its predecessor */
-    uint64_t cur_new = std::min<uint64_t>(chunk_words, P.n16);
-    if (cur_new && !timed_read(fd_d, pin.p[0], (P.diff_off + done_words) * 2, cur_new * 2, 16)) return fail(MTB_ERR_IO, "short read from " + d + "/diffIdx");
+    uint64_t cur_new = std::min<uint64_t>(chunk_words, R.words());
+    if (cur_new && !timed_read(fd_d, pin.p[0], (R.diff_lo + done_words) * 2, cur_new * 2, 16)) return fail(MTB_ERR_IO, "short read from " + d + "/diffIdx");
     int cur = 0;
-    while (done_words < P.n16) {
-        const uint64_t next_off = done_words + cur_new, next_new = std::min<uint64_t>(chunk_words, P.n16 - next_off);
+    while (done_words < R.words()) {
+        const uint64_t next_off = done_words + cur_new, next_new = std::min<uint64_t>(chunk_words, R.words() - next_off);
         bool next_ok = true;
         std::thread reader;
-        if (next_new) reader = std::thread([&, next_off, next_new] { next_ok = timed_read(fd_d, pin.p[cur ^ 1], (P.diff_off + next_off) * 2, next_new * 2, 16); });
+        if (next_new) reader = std::thread([&, next_off, next_new] { next_ok = timed_read(fd_d, pin.p[cur ^ 1], (R.diff_lo + next_off) * 2, next_new * 2, 16); });
         struct Join { std::thread &t; ~Join() { if (t.joinable()) t.join(); } } join_reader{reader};
         const uint16_t *hw = (const uint16_t *)pin.p[cur];
         /* words of a metamer cut by this chunk's end stay for the next one */
@@ -1490,34 +1445,34 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
             hipLaunchKernelGGL(k_diff_tile_count, dim3((uint32_t)tiles), dim3(256), 0, st, (const uint16_t *)d_chunk, n_use, d_tc);
             scan_launch<uint32_t, uint64_t, false>(st, d_tc, tiles, true, d_toff, d_ws);
             STCHK(d2h(c, &n_k, d_toff + tiles, 8));
-            if (!sink && found + n_k > P.expect) return fail(MTB_ERR_IO, "diffIdx holds more metamers than info and split announce (" + std::to_string(P.expect) + ")");
+            if (!sink && found + n_k > R.coded_entries()) return fail(MTB_ERR_IO, "diffIdx holds more metamers than info and split announce (" + std::to_string(R.coded_entries()) + ")");
             if (n_k) {
-                const uint64_t m = std::min<uint64_t>(g + n_k, P.T) - std::min<uint64_t>(g, P.T);       /* entries of the chunk that belong to the index (a dropped last one does not) */
+                const uint64_t m = std::min<uint64_t>(g + n_k, T) - std::min<uint64_t>(g, T);       /* entries of the chunk that belong to the index (a dropped last one does not) */
                 const uint64_t at = sink ? 0 : g;                  /* where the chunk goes in value[] / info[] */
                 /* info entries of the chunk: into the chunk buffer (pack) or straight to their places */
                 if (m) {
-                    if (!timed_read(fd_i, pin.p[2], (P.info_off + g) * 4, m * 4, 16)) return fail(MTB_ERR_IO, "short read from " + d + "/info");
-                    HIPCHK(hipMemcpyAsync(pack ? d_ichunk : ix->d_info + at, pin.p[2], m * 4, hipMemcpyHostToDevice, st));
+                    if (!timed_read(fd_i, pin.p[2], (R.info_lo + g) * 4, m * 4, 16)) return fail(MTB_ERR_IO, "short read from " + d + "/info");
+                    HIPCHK(hipMemcpyAsync(pack ? d_ichunk : d_info + at, pin.p[2], m * 4, hipMemcpyHostToDevice, st));
                 }
-                hipLaunchKernelGGL(k_diff_assemble, dim3((uint32_t)tiles), dim3(256), 0, st, (const uint16_t *)d_chunk, n_use, (const uint64_t *)d_toff, ix->d_values + at);
-                hipLaunchKernelGGL(k_diff_add_carry, dim3(1), dim3(1), 0, st, ix->d_values + at, (const uint64_t *)d_carry);
-                scan_launch<uint64_t, uint64_t, true>(st, ix->d_values + at, n_k, false, ix->d_values + at, d_ws);
+                hipLaunchKernelGGL(k_diff_assemble, dim3((uint32_t)tiles), dim3(256), 0, st, (const uint16_t *)d_chunk, n_use, (const uint64_t *)d_toff, d_values + at);
+                hipLaunchKernelGGL(k_diff_add_carry, dim3(1), dim3(1), 0, st, d_values + at, (const uint64_t *)d_carry);
+                scan_launch<uint64_t, uint64_t, true>(st, d_values + at, n_k, false, d_values + at, d_ws);
                 if (want_dir && m) {
                     const dim3 grid((uint32_t)std::min<uint64_t>((m + 255) / 256, 1u << 16));
-                    hipLaunchKernelGGL(k_dir_chunk_base, grid, dim3(256), 0, st, (const uint64_t *)ix->d_values, g, m, (const uint64_t *)d_carry, L, fmt, nbk, ix->d_dirbase, d_flags);
-                    hipLaunchKernelGGL(k_dir_chunk_fill, grid, dim3(256), 0, st, (const uint64_t *)ix->d_values, g, m, (const uint64_t *)d_carry, L, fmt, nbk,
+                    hipLaunchKernelGGL(k_dir_chunk_base, grid, dim3(256), 0, st, (const uint64_t *)d_values, g, m, (const uint64_t *)d_carry, L, fmt, nbk, ix->d_dirbase, d_flags);
+                    hipLaunchKernelGGL(k_dir_chunk_fill, grid, dim3(256), 0, st, (const uint64_t *)d_values, g, m, (const uint64_t *)d_carry, L, fmt, nbk,
                                        (const uint64_t *)ix->d_dirbase, ix->d_dir, d_flags);
                 }
-                hipLaunchKernelGGL(k_save_last, dim3(1), dim3(1), 0, st, (const uint64_t *)(ix->d_values + at + n_k - 1), d_carry);
+                hipLaunchKernelGGL(k_save_last, dim3(1), dim3(1), 0, st, (const uint64_t *)(d_values + at + n_k - 1), d_carry);
                 if (sink) {
                     HIPCHK(hipEventRecord(sink->ev[1], st));
                     DecodedChunk ck;
                     ck.d_words = d_chunk; ck.n_words = n_use; ck.word0 = done_words - n_carry; ck.d_tile_off = d_toff;
-                    ck.d_values = ix->d_values; ck.n_values = n_k; ck.d_info = ix->d_info; ck.n_info = m; ck.first_entry = g;
+                    ck.d_values = d_values; ck.n_values = n_k; ck.d_info = d_info; ck.n_info = m; ck.first_entry = g;
                     STCHK(sink->on_chunk(ck));
                     HIPCHK(hipEventRecord(sink->ev[2], st));
                 }
-                if (pack && m) hipLaunchKernelGGL(k_index_pack_chunk, dim3((uint32_t)std::min<uint64_t>((m + 255) / 256, 1u << 16)), dim3(256), 0, st, ix->d_values, (const uint32_t *)d_ichunk, g, m, fmt);
+                if (pack && m) hipLaunchKernelGGL(k_index_pack_chunk, dim3((uint32_t)std::min<uint64_t>((m + 255) / 256, 1u << 16)), dim3(256), 0, st, d_values, (const uint32_t *)d_ichunk, g, m, fmt);
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(st));          /* the pinned buffers are refilled next */
                 if (sink) {
@@ -1527,9 +1482,9 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
                     sink->n_chunks++;
                 }
                 g += n_k; found += n_k;
-                if (ix->open_chunks < 4 || (ix->open_chunks & 63u) == 0) {        /* (a driver query: not for every one of thousands of tiny test chunks) */
+                if (ix && (ix->open_chunks < 4 || (ix->open_chunks & 63u) == 0)) {        /* (a driver query: not for every one of thousands of tiny test chunks) */
                     size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) == hipSuccess && ix->open_free0 > fr) ix->open_peak_bytes = std::max<uint64_t>(ix->open_peak_bytes, ix->open_free0 - fr); }
-                ix->open_chunks++;
+                if (ix) ix->open_chunks++;
             }
         }
         for (uint32_t k = 0; k < tail; k++) carry_w[k] = hw[cur_new - tail + k];
@@ -1541,21 +1496,21 @@ static mtb_status decode_chunked(mtb_ctx *c, mtb_index *ix, const std::string &d
         done_words = next_off; cur_new = next_new; cur ^= 1;
     }
     if (sink) sink->n_entries = found;
-    else if (found != P.expect)    /* validateDatabase.cpp:17-142: #terminators must equal #info entries */
-        return fail(MTB_ERR_IO, "diffIdx holds " + std::to_string(found) + " metamers where info and split announce " + std::to_string(P.expect));
+    else if (found != R.coded_entries())    /* validateDatabase.cpp:17-142: #terminators must equal #info entries */
+        return fail(MTB_ERR_IO, "diffIdx holds " + std::to_string(found) + " metamers where info and split announce " + std::to_string(R.coded_entries()));
     if (want_dir) {
         /* (*d_carry = the last decoded value; with a dropped last entry the index's own last flat value is one before it: re-read it) */
-        if (P.T && g > P.T) {
+        if (T && g > T) {
             if (pack) return fail(MTB_ERR_UNSUPPORTED, "pack on load of a range whose last coded metamer is dropped");       /* (never chosen: see open_impl) */
-            hipLaunchKernelGGL(k_save_last, dim3(1), dim3(1), 0, st, (const uint64_t *)(ix->d_values + P.T - 1), d_carry);
+            hipLaunchKernelGGL(k_save_last, dim3(1), dim3(1), 0, st, (const uint64_t *)(d_values + T - 1), d_carry);
         }
-        hipLaunchKernelGGL(k_dir_finish, dim3(64), dim3(256), 0, st, (const uint64_t *)d_carry, P.T, L, fmt, nbk, n_groups, ix->d_dirbase, ix->d_dir, d_flags, 0);
-        hipLaunchKernelGGL(k_dir_finish, dim3(4096), dim3(256), 0, st, (const uint64_t *)d_carry, P.T, L, fmt, nbk, n_groups, ix->d_dirbase, ix->d_dir, d_flags, 1);
+        hipLaunchKernelGGL(k_dir_finish, dim3(64), dim3(256), 0, st, (const uint64_t *)d_carry, T, L, fmt, nbk, n_groups, ix->d_dirbase, ix->d_dir, d_flags, 0);
+        hipLaunchKernelGGL(k_dir_finish, dim3(4096), dim3(256), 0, st, (const uint64_t *)d_carry, T, L, fmt, nbk, n_groups, ix->d_dirbase, ix->d_dir, d_flags, 1);
         HIPCHK(hipGetLastError());
         uint32_t fl[2] = {0, 0};
         STCHK(d2h(c, fl, d_flags, 8));
         if (fl[0] || fl[1]) { hipError_t e = hipFree(ix->d_dir); e = hipFree(ix->d_dirbase); (void)e; ix->d_dir = nullptr; ix->d_dirbase = nullptr; }
-        else { ix->dir_L = L; ix->dir_buckets = nbk; *dir_ok = true; }
+        else { ix->dir_L = L; ix->dir_buckets = nbk; dir->dir_ok = true; }
     }
     HIPCHK(hipStreamSynchronize(st));
     return MTB_OK;
@@ -1579,8 +1534,8 @@ static size_t open_make_room(mtb_ctx *c) {
     return fr;
 }
 
-/* the taxonomy of a database directory and its species table (KmerMatcher::loadTaxIdList: built from the ids of taxID_list, which
- * *ids receives): taxonomyDB if `have_bin` and it loads, else the dump files of `taxdir` (an unreadable taxonomyDB: DBDIR/taxonomy) */
+/* the taxonomy of a database directory and the ids of its taxID_list (the species table is built from them, KmerMatcher::
+ * loadTaxIdList: build_tax2species): taxonomyDB if `have_bin` and it loads, else the dump files of `taxdir` (an unreadable taxonomyDB: DBDIR/taxonomy) */
 static mtb_status load_database_taxonomy(const std::string &d, std::string taxdir, bool have_bin, mtbhost::Taxonomy *tax, std::vector<int32_t> *ids) {
     std::string err;
     bool tax_ok = false;
@@ -1594,7 +1549,6 @@ static mtb_status load_database_taxonomy(const std::string &d, std::string taxdi
     }
     if (!tax_ok && !mtbhost::load_taxonomy(taxdir, tax, &err)) return fail(MTB_ERR_IO, err);
     if (!mtbhost::read_taxid_list(d + "/taxID_list", ids)) return fail(MTB_ERR_IO, "cannot open " + d + "/taxID_list");
-    mtbhost::build_tax2species(tax, ids->data(), ids->size());
     return MTB_OK;
 }
 
@@ -1613,9 +1567,10 @@ static mtb_status open_impl(mtb_ctx *c, const char *dbdir, const char *taxonomy_
     const bool have_bin = mtbhost::file_exists(d + "/taxonomyDB");
     if (!have_bin && !mtbhost::file_exists(taxdir + "/nodes.dmp"))
         return fail(MTB_ERR_IO, "no taxonomy: neither " + d + "/taxonomyDB nor dump files in " + taxdir);
-    PartPlan plan;
+    mtbhost::PartPlan plan;
     STCHK(plan_parts(d, n_parts, &plan));
-    const PartPlan::P &P = plan.parts[part];
+    const bool empty = plan.parts[part].empty;
+    const mtbhost::MergeSlice &R = plan.parts[part].r;
     mtb_index *ix = new mtb_index();
     /* every early return below hands the index (and what it holds on the device) back */
     struct Guard { mtb_index *ix; ~Guard() { if (ix) mtb_index_close(ix); } } guard{ix};
@@ -1623,16 +1578,13 @@ static mtb_status open_impl(mtb_ctx *c, const char *dbdir, const char *taxonomy_
     for (uint32_t q = part + 1; q < n_parts; q++) if (!plan.parts[q].empty) ix->match_last = true;
     std::vector<int32_t> ids;
     STCHK(load_database_taxonomy(d, taxdir, have_bin, &ix->tax, &ids));
-    ix->info_mask = ~((uint32_t)(params->skip_redundancy == 0) << 31);   /* KmerMatcher.cpp:204-205 */
+    mtbhost::build_tax2species(&ix->tax, ids.data(), ids.size());
+    ix->info_mask = legacy_info_mask(params->skip_redundancy);
     STCHK(upload_taxonomy(ix));
-    if (P.empty) { ix->T = 0; guard.ix = nullptr; *out = ix; return MTB_OK; }
+    if (empty) { ix->T = 0; guard.ix = nullptr; *out = ix; return MTB_OK; }
     /* only this partition's byte ranges are read from the files, chunk by chunk through pinned buffers straight into HBM (the next
      * chunk is read while the device decodes the current one): no whole-file copy in host OR device memory, whatever the database size */
-    OpenPlan O;
-    O.n16 = P.diff_hi - P.diff_lo; O.T = P.info_hi - P.info_lo; O.lead = P.explicit_first ? 1 : 0;
-    O.expect = O.T - O.lead + (P.drop_last ? 1 : 0);     /* metamers coded in the byte range */
-    O.diff_off = P.diff_lo; O.info_off = P.info_lo; O.first_value = P.ad;
-    const uint64_t T = O.T;
+    const uint64_t T = R.records();
     /* the directory this index will have (build_directory's rule), decided before the load so that it is built chunk by chunk */
     int L = 1;
     while (L < 7 && (uint64_t)mtb_pow21(L) < T / 8) L++;
@@ -1644,16 +1596,16 @@ static mtb_status open_impl(mtb_ctx *c, const char *dbdir, const char *taxonomy_
         HIPCHK(hipMemGetInfo(&fr, &tot));
         const uint32_t nbk = mtb_pow21(L);
         /* directory + target words + (flat state) info[] + the chunk buffers of the decode */
-        const bool pack_guess = L == 7 && !P.drop_last && !c->opt.no_pack && (c->opt.open_packed >= 0 ? c->opt.open_packed != 0 : T >= (1ull << 28));
+        const bool pack_guess = L == 7 && !R.drop_last && !c->opt.no_pack && (c->opt.open_packed >= 0 ? c->opt.open_packed != 0 : T >= (1ull << 28));
         const size_t need_dir = ((size_t)nbk + 1) * 4 + ((size_t)(nbk >> 16) + 3) * 8 + (T + 1) * 8 + (64u << 20);
-        const size_t need_all = need_dir + (pack_guess ? 0 : (size_t)T * 4) + (std::min<uint64_t>(O.n16, 1ull << 27) * 12 + (64u << 20));
+        const size_t need_all = need_dir + (pack_guess ? 0 : (size_t)T * 4) + (std::min<uint64_t>(R.words(), 1ull << 27) * 12 + (64u << 20));
         if (need_all > fr && held_bytes(c, BUF_FIXED) > 0) fr = open_make_room(c);      /* a reservation made for the first batches must not cost the index its directory */
         if (need_dir > fr) want_dir = false;        /* no room next to the values: the bisection join still works */
     }
     /* pack on load: big databases (>= 2^28 targets; MTB_OPEN_PACKED=1 / 0 forces it on toy databases / off) whose directory has depth 7
      * open in the SEALED state -- packed 8-byte words, info[] never resident (mtb_index_seal's state; everything that needs the flat
      * arrays unpacks on demand as for any sealed index) */
-    bool pack = want_dir && L == 7 && !P.drop_last && !c->opt.no_pack && (c->opt.open_packed >= 0 ? c->opt.open_packed != 0 : T >= (1ull << 28));
+    bool pack = want_dir && L == 7 && !R.drop_last && !c->opt.no_pack && (c->opt.open_packed >= 0 ? c->opt.open_packed != 0 : T >= (1ull << 28));
     { size_t fr = 0, tot = 0; HIPCHK(hipMemGetInfo(&fr, &tot)); ix->open_free0 = fr; }
     for (int attempt = 0; attempt < 2; attempt++) {
         ix->open_chunks = 0; ix->open_peak_bytes = 0;
@@ -1667,12 +1619,10 @@ static mtb_status open_impl(mtb_ctx *c, const char *dbdir, const char *taxonomy_
                 HIPCHK(e);
             }
         }
-        bool dir_ok = false;
-        {   /* the chunk buffers go back whatever way the decode ends */
-            struct Scratch { mtb_ctx *c; ~Scratch() { release(c, "diffraw"); release(c, "difftc"); release(c, "difftoff"); release(c, "infochunk"); } } scratch{c};
-            STCHK(decode_chunked(c, ix, d, O, want_dir, L, pack, &dir_ok));
-        }
-        if (pack && !dir_ok) {      /* a letter >= 21 or a bucket group of 2^32 targets: no directory, hence no packed state -- once more, flat */
+        OpenDirectory dir; dir.ix = ix; dir.want_dir = want_dir; dir.L = L; dir.pack = pack;
+        {   DecodeScratch scratch{c};
+            STCHK(decode_chunked(c, params->kmer_format, d, R, ix->d_values, ix->d_info, &dir)); }
+        if (pack && !dir.dir_ok) {      /* a letter >= 21 or a bucket group of 2^32 targets: no directory, hence no packed state -- once more, flat */
             hipError_t e = hipFree(ix->d_values); (void)e; ix->d_values = nullptr;
             pack = false;
             continue;
@@ -1697,7 +1647,7 @@ mtb_status mtb_index_open_part(mtb_ctx *c, const char *dbdir, const char *taxono
 }
 mtb_status mtb_index_part_bounds(const char *dbdir, uint32_t n_parts, uint64_t *bounds) {
     if (!dbdir || !bounds || n_parts == 0) return fail(MTB_ERR_ARG, "NULL argument");
-    PartPlan plan;
+    mtbhost::PartPlan plan;
     STCHK(plan_parts(dbdir, n_parts, &plan));
     for (uint32_t p = 0; p < n_parts; p++) bounds[p] = plan.bounds[p];
     return MTB_OK;
@@ -1712,7 +1662,7 @@ mtb_status mtb_index_from_device(mtb_ctx *c, uint64_t *d_values, uint32_t *d_inf
     std::string err;
     if (!mtbhost::load_taxonomy(taxonomy_dir, &ix->tax, &err)) { delete ix; return fail(MTB_ERR_IO, err); }
     mtbhost::build_tax2species(&ix->tax, taxid_list, n_taxids);
-    ix->info_mask = ~((uint32_t)(params->skip_redundancy == 0) << 31);
+    ix->info_mask = legacy_info_mask(params->skip_redundancy);
     ix->d_values = d_values; ix->d_info = d_info; ix->T = n_targets;
     mtb_status st = upload_taxonomy(ix);
     if (st != MTB_OK) { mtb_index_close(ix); return st; }
@@ -1963,16 +1913,14 @@ mtb_status mtb_index_download(mtb_index *ix, uint64_t *values, uint32_t *info, u
  * first entry of an append is coded against the last value written before it), the coded slice and its info entries cross PCIe into
  * pinned buffers and a writer thread appends them to the files while the next slice is coded; the taxID_list map accumulates.
  * finish(): the split checkpoints -- armed at every size_of_split-th entry, recorded at the first later entry of another amino-acid
- * part -- need n, which only the end knows: every slice left a restart record {entry, word offset, previous value}, and the slices
- * that hold an arming are looked at again -- in the caller's array if it is still resident, else re-decoded from the diffIdx just
- * written, from exactly that record (decode_chunked).  An arming still pending at a slice's end is resolved in the next slice.
+ * part -- need n, which only the end knows: every slice left the range of the files it became (its own checkpoint: the value
+ * before it), and the slices that hold an arming are looked at again -- in the caller's array if it is still resident, else re-decoded
+ * from the diffIdx just written, as exactly that range (decode_chunked).  An arming still pending at a slice's end is resolved in the next slice.
  * db.parameters is removed first and written last: a directory whose write failed cannot be opened as a database. */
 struct IndexWriter {
-    struct Split { uint64_t ad, diff_off, info_off; };
-    struct Restart { uint64_t entry, word, prev, m, words; };        /* a slice: first entry, first word, the value before it, entries, words */
     mtb_ctx *c = nullptr; std::string d; int fd = -1, fi = -1; int32_t max_id = 0; mtb_params params;
     uint64_t SLICE = 0, n = 0, diff_count = 0, last_value = 0;
-    std::vector<Restart> restarts;
+    std::vector<mtbhost::MergeSlice> slices;        /* a written slice's m entries are the range's coded ones; it leads with the entry before them (none before entry 0) */
     const uint64_t *resident = nullptr;          /* the one appended array, if it stays on the device until finish() (mtb_index_write) */
     uint32_t *d_nw = nullptr; uint64_t *d_off = nullptr; uint16_t *d_enc = nullptr; uint8_t *d_seen = nullptr; int32_t *d_extra = nullptr; uint32_t *d_nextra = nullptr;
     void *pin_e[2] = {nullptr, nullptr}, *pin_i[2] = {nullptr, nullptr};
@@ -2021,7 +1969,9 @@ struct IndexWriter {
             uint64_t words = 0, slice_last = 0;
             STCHK(d2h(c, &words, d_off + mm, 8));
             STCHK(d2h(c, &slice_last, d_values + s0 + mm - 1, 8));
-            restarts.push_back(Restart{n + s0, diff_count, slice_prev, mm, words});
+            {   mtbhost::MergeSlice r;
+                r.lead = n + s0 ? 1 : 0; r.first_value = slice_prev; r.diff_lo = diff_count; r.diff_hi = diff_count + words; r.info_lo = n + s0 - r.lead; r.info_hi = n + s0 + mm;
+                slices.push_back(r); }
             slice_prev = slice_last;
             if (writers[cur].joinable()) writers[cur].join();  /* (two slices back: its buffers are `cur`'s) */
             if (!write_ok) return fail(MTB_ERR_IO, "short write while writing " + d);
@@ -2048,33 +1998,30 @@ struct IndexWriter {
     }
     /* the checkpoints: j[k] for every arming position k * size_of_split - 1; equal neighbours are one checkpoint (an arming inside a
      * run that is still armed changes nothing); at most split_num - 1 are kept */
-    mtb_status find_splits(int split_num, std::vector<Split> *splits) {
+    mtb_status find_splits(int split_num, std::vector<mtbhost::MergeCheckpoint> *splits) {
         hipStream_t st = c->stream;
         const uint64_t size_of_split = n / (uint64_t)(split_num - 1);
         if (!size_of_split || !n) return MTB_OK;
         const uint64_t n_k = std::min<uint64_t>(n / size_of_split, 1u << 24);
         size_t n_cp = 0; uint64_t last_j = UINT64_MAX; bool pending = false;
         std::vector<uint64_t> armed, hj, cpj, cpv, cpo;
-        struct Scratch { mtb_ctx *c; ~Scratch() { release(c, "wdecv"); release(c, "wdeci"); release(c, "wsplitj"); release(c, "wcp"); release(c, "diffraw"); release(c, "difftc"); release(c, "difftoff"); } } scratch{c};
-        for (size_t r = 0; r < restarts.size() && n_cp + 1 < (size_t)split_num; r++) {
-            const Restart &R = restarts[r];
-            const uint64_t e = R.entry, end = R.entry + R.m;
+        struct Scratch { mtb_ctx *c; ~Scratch() { release(c, "wdecv"); release(c, "wdeci"); release(c, "wsplitj"); release(c, "wcp"); } } scratch{c};
+        DecodeScratch decode_scratch{c};
+        for (size_t r = 0; r < slices.size() && n_cp + 1 < (size_t)split_num; r++) {
+            const mtbhost::MergeSlice &R = slices[r];
+            const uint64_t e = R.info_lo + R.lead, m = R.coded_entries(), end = R.info_hi, prev = R.first_value;
             armed.clear();
             if (pending) armed.push_back(e - 1);                    /* still armed at the previous slice's last entry: every entry since the arming shares its amino-acid part */
             pending = false;
             const uint64_t k_lo = std::max<uint64_t>(1, (e + 1 + size_of_split - 1) / size_of_split), k_hi = std::min<uint64_t>(n_k, end / size_of_split);
             for (uint64_t k = k_lo; k <= k_hi; k++) armed.push_back(k * size_of_split - 1);
             if (armed.empty()) continue;
-            const uint64_t lead = e ? 1 : 0;
             const uint64_t *vg = resident;                            /* indexed by the entry's number in the whole output */
             if (!vg) {
                 uint64_t *dv; uint32_t *di;
-                STCHK(ensure(c, "wdecv", R.m + 2, &dv)); STCHK(ensure(c, "wdeci", R.m + 2, &di));
-                mtb_index tmp; tmp.ctx = c; tmp.params = params; tmp.d_values = dv; tmp.d_info = di;
-                OpenPlan P; P.n16 = R.words; P.T = R.m + lead; P.expect = R.m; P.lead = lead; P.diff_off = R.word; P.info_off = e - lead; P.first_value = R.prev;
-                bool dir_ok = false;
-                STCHK(decode_chunked(c, &tmp, d, P, false, 1, false, &dir_ok));
-                vg = dv - (e - lead);
+                STCHK(ensure(c, "wdecv", m + 2, &dv)); STCHK(ensure(c, "wdeci", m + 2, &di));
+                STCHK(decode_chunked(c, params.kmer_format, d, R, dv, di));
+                vg = dv - R.info_lo;
             }
             const uint32_t na = (uint32_t)armed.size();
             uint64_t *d_j, *d_ws, *d_cp;
@@ -2095,20 +2042,20 @@ struct IndexWriter {
             STCHK(ensure(c, "wcp", 3 * (size_t)q, &d_cp));
             STCHK(ensure(c, "scanws", scan_ws_elems(SLICE + 1), &d_ws));
             STCHK(h2d(c, d_cp, cpj.data(), (size_t)q * 8));
-            hipLaunchKernelGGL(k_diff_nwords, dim3((uint32_t)((R.m + 255) / 256)), dim3(256), 0, st, vg, e, R.m, R.prev, d_nw);
-            scan_launch<uint32_t, uint64_t, false>(st, d_nw, R.m, true, d_off, d_ws);
+            hipLaunchKernelGGL(k_diff_nwords, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, vg, e, m, prev, d_nw);
+            scan_launch<uint32_t, uint64_t, false>(st, d_nw, m, true, d_off, d_ws);
             hipLaunchKernelGGL(k_split_gather, dim3((q + 63) / 64), dim3(64), 0, st, vg, (const uint64_t *)d_off, e, (const uint64_t *)d_cp, q, d_cp + q, d_cp + 2 * (size_t)q);
             HIPCHK(hipGetLastError());
             cpv.resize(q); cpo.resize(q);
             STCHK(d2h(c, cpv.data(), d_cp + q, (size_t)q * 8)); STCHK(d2h(c, cpo.data(), d_cp + 2 * (size_t)q, (size_t)q * 8));
-            for (uint32_t t = 0; t < q; t++) (*splits)[++n_cp] = Split{cpv[t], R.word + cpo[t], cpj[t] + 1};
+            for (uint32_t t = 0; t < q; t++) (*splits)[++n_cp] = mtbhost::MergeCheckpoint{cpv[t], R.diff_lo + cpo[t], cpj[t] + 1};
         }
         return MTB_OK;
     }
     mtb_status finish(int split_num) {
         join();
         if (!write_ok) return fail(MTB_ERR_IO, "short write while writing " + d);
-        std::vector<Split> splits((size_t)split_num, Split{0, 0, 0});
+        std::vector<mtbhost::MergeCheckpoint> splits((size_t)split_num, mtbhost::MergeCheckpoint{0, 0, 0});
         STCHK(find_splits(split_num, &splits));
         std::vector<uint8_t> seen((size_t)max_id + 2, 0);
         STCHK(d2h(c, seen.data(), d_seen, seen.size()));
@@ -2118,7 +2065,7 @@ struct IndexWriter {
         std::vector<int32_t> extra_ids(n_extra);           /* ids outside the taxonomy's range (kept for taxID_list) */
         if (n_extra) STCHK(d2h(c, extra_ids.data(), d_extra, (size_t)n_extra * 4));
         FILE *f = fopen((d + "/split").c_str(), "wb"); if (!f) return fail(MTB_ERR_IO, "cannot create " + d + "/split");
-        fwrite(splits.data(), sizeof(Split), splits.size(), f); fclose(f);
+        fwrite(splits.data(), sizeof(mtbhost::MergeCheckpoint), splits.size(), f); fclose(f);
         std::sort(extra_ids.begin(), extra_ids.end()); extra_ids.erase(std::unique(extra_ids.begin(), extra_ids.end()), extra_ids.end());
         f = fopen((d + "/taxID_list").c_str(), "w"); if (!f) return fail(MTB_ERR_IO, "cannot create " + d + "/taxID_list");
         {   size_t e = 0;
@@ -3809,6 +3756,48 @@ static mtb_status builder_check_taxids(const mtb_builder *b, const int32_t *taxi
 }
 static dim3 grid256(uint64_t n) { return dim3((uint32_t)((n + 255) / 256)); }
 
+/* Records keyed (species, taxid) above the value (k_build_keys, k_merge_sort_key) into the order (value, species, taxid): a stable sort
+ * by (species, taxid), the swap of the key's halves back into `rec`, a stable sort by every bit.  dev_sort's other buffer is "kmersB";
+ * *sorted = where the result lies.  `between`, if given, is recorded between the two sorts. */
+static mtb_status dev_sort_groups(mtb_ctx *c, mtb_kmer *rec, uint64_t n, int bits, mtb_kmer **sorted, hipEvent_t between = nullptr) {
+    STCHK(dev_sort(c, rec, n, mtb_build_key_first_bit(bits), sorted, nullptr, 0));
+    hipLaunchKernelGGL(k_build_swap, grid256(n), dim3(256), 0, c->stream, (const mtb_kmer *)*sorted, n, bits, rec);
+    HIPCHK(hipGetLastError());
+    if (between) HIPCHK(hipEventRecord(between, c->stream));
+    return dev_sort(c, rec, n, /* every bit */ 0, sorted, nullptr, 0);
+}
+
+/* Records in that order -> one entry per (value, species) group, its info the LCA of the group's taxids: heads -> scan -> the group
+ * count G, for which `arrays` names the output (G + 1 values, G info entries; the builder allocates its index there, the merge takes
+ * workspace) -> k_build_reduce, and k_build_reduce_long for the groups that one listed as too long for a lane. */
+static mtb_status dev_reduce_groups(mtb_ctx *c, const mtb_kmer *d_s, uint64_t n, const mtb_tax_view &tv,
+                                    const std::function<mtb_status(uint64_t groups, uint64_t **d_values, uint32_t **d_info)> &arrays, uint64_t *G, uint32_t *n_long) {
+    hipStream_t st = c->stream;
+    uint32_t *d_head, *d_pos, *d_list; uint64_t *d_ws;
+    STCHK(ensure(c, "bhead", n, &d_head)); STCHK(ensure(c, "bpos", n + 1, &d_pos));
+    STCHK(ensure(c, "scanws", scan_ws_elems(n + 1), &d_ws));
+    hipLaunchKernelGGL(k_build_heads, grid256(n), dim3(256), 0, st, d_s, n, d_head);
+    scan_launch<uint32_t, uint32_t, false>(st, d_head, n, true, d_pos, (uint32_t *)d_ws);
+    HIPCHK(hipGetLastError());
+    uint32_t n_groups = 0;
+    STCHK(d2h(c, &n_groups, d_pos + n, 4));
+    *G = n_groups;
+    uint64_t *d_values = nullptr; uint32_t *d_info = nullptr;
+    STCHK(arrays(*G, &d_values, &d_info));
+    STCHK(ensure(c, "blist", n / (MTB_BUILD_LANE_MAX + 1) + 2, &d_list));
+    uint32_t *d_nlist = scal<uint32_t>(c, SC_JOIN_COUNT);
+    HIPCHK(scal_clear(c, SC_JOIN_COUNT));
+    hipLaunchKernelGGL(k_build_reduce, grid256(n), dim3(256), 0, st, d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv, d_values, d_info, d_list, d_nlist);
+    HIPCHK(hipGetLastError());
+    STCHK(d2h(c, n_long, d_nlist, 4));
+    if (*n_long) {
+        hipLaunchKernelGGL(k_build_reduce_long, dim3(std::min<uint32_t>(*n_long, 1u << 16)), dim3(64), 0, st, d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv,
+                           d_values, d_info, (const uint32_t *)d_list, (const uint32_t *)d_nlist);
+        HIPCHK(hipGetLastError());
+    }
+    return MTB_OK;
+}
+
 extern "C" {
 
 mtb_status mtb_builder_create(mtb_ctx *c, const char *taxonomy_dir, const mtb_params *params, mtb_builder **out) {
@@ -3996,38 +3985,15 @@ mtb_status mtb_builder_finish(mtb_builder *b, mtb_index **out) {
     hipLaunchKernelGGL(k_build_keys, grid256(n), dim3(256), 0, st, (const mtb_kmer *)b->d_rec, n, (const int32_t *)ix->d_tax2species, b->tax.max_id, bits, d_a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev[1], st));
-    STCHK(dev_sort(c, d_a, n, mtb_build_key_first_bit(bits), &d_s, nullptr, 0));      /* stable: (species, taxid) */
-    hipLaunchKernelGGL(k_build_swap, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, bits, d_a);     /* always into "kmersA": dev_sort's other buffer is "kmersB" */
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev[2], st));
-    STCHK(dev_sort(c, d_a, n, /* every bit */ 0, &d_s, nullptr, 0));                 /* stable: (value, species, taxid) */
+    STCHK(dev_sort_groups(c, d_a, n, bits, &d_s, ev[2]));
     HIPCHK(hipEventRecord(ev[3], st));
-    uint32_t *d_head, *d_pos, *d_list; uint64_t *d_ws;
-    STCHK(ensure(c, "bhead", n, &d_head)); STCHK(ensure(c, "bpos", n + 1, &d_pos));
-    STCHK(ensure(c, "scanws", scan_ws_elems(n + 1), &d_ws));
-    hipLaunchKernelGGL(k_build_heads, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, d_head);
-    scan_launch<uint32_t, uint32_t, false>(st, d_head, n, true, d_pos, (uint32_t *)d_ws);
-    HIPCHK(hipGetLastError());
-    uint32_t n_groups = 0;
-    STCHK(d2h(c, &n_groups, d_pos + n, 4));
-    HIPCHK(hipEventRecord(ev[4], st));
-    const uint64_t G = n_groups;
-    {   hipError_t e = hipMalloc((void **)&ix->d_values, (G + 1) * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&ix->d_info, std::max<uint64_t>(G, 1) * 4);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(MTB_ERR_OOM, "not enough HBM for the built index (" + std::to_string(G) + " entries)"); } }
-    STCHK(ensure(c, "blist", n / (MTB_BUILD_LANE_MAX + 1) + 2, &d_list));
-    uint32_t *d_nlist = scal<uint32_t>(c, SC_JOIN_COUNT);
-    HIPCHK(scal_clear(c, SC_JOIN_COUNT));
-    const mtb_tax_view tv = tax_view(ix);
-    hipLaunchKernelGGL(k_build_reduce, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv, ix->d_values, ix->d_info, d_list, d_nlist);
-    HIPCHK(hipGetLastError());
-    uint32_t n_long = 0;
-    STCHK(d2h(c, &n_long, d_nlist, 4));
-    if (n_long) {
-        hipLaunchKernelGGL(k_build_reduce_long, dim3(std::min<uint32_t>(n_long, 1u << 16)), dim3(64), 0, st, (const mtb_kmer *)d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv,
-                           ix->d_values, ix->d_info, (const uint32_t *)d_list, (const uint32_t *)d_nlist);
-        HIPCHK(hipGetLastError());
-    }
+    uint64_t G = 0; uint32_t n_long = 0;
+    STCHK(dev_reduce_groups(c, d_s, n, tax_view(ix), [&](uint64_t groups, uint64_t **d_values, uint32_t **d_info) -> mtb_status {
+        HIPCHK(hipEventRecord(ev[4], st));
+        hipError_t e = hipMalloc((void **)&ix->d_values, (groups + 1) * 8);
+        if (e == hipSuccess) e = hipMalloc((void **)&ix->d_info, std::max<uint64_t>(groups, 1) * 4);
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(MTB_ERR_OOM, "not enough HBM for the built index (" + std::to_string(groups) + " entries)"); }
+        *d_values = ix->d_values; *d_info = ix->d_info; return MTB_OK; }, &G, &n_long));
     HIPCHK(hipEventRecord(ev[5], st));
     HIPCHK(hipStreamSynchronize(st));
     for (int k = 0; k < 5; k++) { float ms = 0; if (hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) (void)hipGetLastError(); b->ms[k] = ms; }
@@ -4092,7 +4058,7 @@ static mtb_status dev_merge_tree(mtb_ctx *c, mtb_kmer *ping, mtb_kmer *pong, std
 }
 
 namespace {
-struct MergeSource { std::string dir; uint32_t info_mask = 0xFFFFFFFFu; mtbhost::MergeInput plan; };
+struct MergeSource { std::string dir; uint32_t info_mask = 0xFFFFFFFFu; };
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 }
 
@@ -4136,7 +4102,7 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
         if (reduced_aa) return fail(MTB_ERR_UNSUPPORTED, "database " + s.dir + " was built with the reduced amino-acid alphabet (Reduced_alphabet 1 in db.parameters); not implemented");
         if (q.kmer_format != params->kmer_format || (q.syncmer != 0) != (params->syncmer != 0) || (params->syncmer && q.smer_len != params->smer_len))
             return fail(MTB_ERR_ARG, "kmer_format / syncmer / smer_len of " + s.dir + " differ from the merge's parameters");
-        s.info_mask = ~((uint32_t)(q.skip_redundancy == 0) << 31);       /* legacy databases: bit 31 is a flag (IndexCreator.h:355, 400) */
+        s.info_mask = legacy_info_mask(q.skip_redundancy);
         struct stat sd, si;
         if (stat((s.dir + "/diffIdx").c_str(), &sd) != 0 || stat((s.dir + "/info").c_str(), &si) != 0) return fail(MTB_ERR_IO, "cannot open diffIdx / info in " + s.dir);
         std::vector<mtbhost::MergeCheckpoint> sp;
@@ -4146,18 +4112,18 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
     }
     /* the taxonomy of the merge, on the device: a holder index without targets.  The species table covers every node: for an id that
      * occurs it holds what the table built from the ids that occur (mtb_builder_finish) holds. */
-    mtb_index *hold = new mtb_index();
-    struct Guard { mtb_index *ix; ~Guard() { mtb_index_close(ix); } } guard{hold};
-    hold->ctx = c; hold->params = *params; hold->params.skip_redundancy = 1; hold->own = true;
+    mtb_index *hold = nullptr;
     {   std::string err;
         mtb_params q = *params; int reduced_aa = 0;
         mtbhost::load_db_parameters(std::string(taxonomy_dir) + "/..", &q, &reduced_aa);
         if (reduced_aa) return fail(MTB_ERR_UNSUPPORTED, "Reduced_alphabet 1 is not implemented");
-        if (!mtbhost::load_taxonomy(taxonomy_dir, &hold->tax, &err)) return fail(MTB_ERR_IO, err);
+        mtbhost::Taxonomy tax;
+        if (!mtbhost::load_taxonomy(taxonomy_dir, &tax, &err)) return fail(MTB_ERR_IO, err);
         std::vector<int32_t> ids;
-        for (int32_t t = 0; t <= hold->tax.max_id; t++) if (hold->tax.cn(t) >= 0) ids.push_back(t);
-        mtbhost::build_tax2species(&hold->tax, ids.data(), ids.size()); }
-    STCHK(upload_taxonomy(hold));
+        for (int32_t t = 0; t <= tax.max_id; t++) if (tax.cn(t) >= 0) ids.push_back(t);
+        q = *params; q.skip_redundancy = 1;
+        STCHK(tax_holder_index(c, q, std::move(tax), ids, &hold)); }
+    struct Guard { mtb_index *ix; ~Guard() { mtb_index_close(ix); } } guard{hold};
     const mtb_tax_view tv = tax_view(hold);
     const int bits = mtb_build_tax_bits(hold->tax.max_id);
     /* the ranges */
@@ -4180,7 +4146,8 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
     S.n_ranges = ranges.size(); S.max_range_records_used = max_rec;
     IndexWriter w;
     STCHK(w.begin(c, outdir, hold->tax.max_id, hold->params, max_rec));
-    struct Scratch { mtb_ctx *c; ~Scratch() { for (const char *nm : {"mrgA", "mrgB", "mrgsplit", "mrgov", "mrgoi", "bhead", "bpos", "blist", "diffraw", "difftc", "difftoff", "kmersB", "hist"}) release(c, nm); } } scratch{c};
+    struct Scratch { mtb_ctx *c; ~Scratch() { for (const char *nm : {"mrgA", "mrgB", "mrgsplit", "mrgov", "mrgoi", "bhead", "bpos", "blist", "kmersB", "hist"}) release(c, nm); } } scratch{c};
+    DecodeScratch decode_scratch{c};
     unsigned long long *d_bad = scal<unsigned long long>(c, SC_JOIN_COUNT);
     uint32_t *d_unsorted = scal<uint32_t>(c, SC_JOIN_OVERFLOW);
     uint64_t *d_trim = scal<uint64_t>(c, SC_N_LARGE);                  /* two words: SC_N_LARGE, SC_MAX_SEG */
@@ -4196,11 +4163,7 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
             if (T == 0) continue;
             /* the slice is decoded into the buffer the merge has not written yet: T + 1 values, then T info entries */
             uint64_t *dv = (uint64_t *)d_b; uint32_t *di = (uint32_t *)(dv + T + 1);
-            mtb_index tmp; tmp.ctx = c; tmp.params = *params; tmp.d_values = dv; tmp.d_info = di;
-            OpenPlan P; P.n16 = sl.diff_hi - sl.diff_lo; P.T = T; P.lead = sl.lead; P.expect = T - sl.lead + (sl.drop_last ? 1 : 0);
-            P.diff_off = sl.diff_lo; P.info_off = sl.info_lo; P.first_value = sl.first_value;
-            bool dir_ok = false;
-            STCHK(decode_chunked(c, &tmp, src[i].dir, P, false, 1, false, &dir_ok));
+            STCHK(decode_chunked(c, params->kmer_format, src[i].dir, sl, dv, di));
             hipLaunchKernelGGL(k_merge_trim, dim3(1), dim3(64), 0, st, (const uint64_t *)dv, T, R.lo, R.hi, d_trim);
             HIPCHK(hipGetLastError());
             uint64_t ab[2] = {0, 0};
@@ -4224,9 +4187,7 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
                 /* built under another taxonomy: not ascending under this one -- the builder's two radix sorts, for this slice alone */
                 mtb_kmer *d_s;
                 hipLaunchKernelGGL(k_merge_sort_key, grid256(cnt), dim3(256), 0, st, rec, cnt, bits);
-                STCHK(dev_sort(c, rec, cnt, mtb_build_key_first_bit(bits), &d_s, nullptr, 0));
-                hipLaunchKernelGGL(k_build_swap, grid256(cnt), dim3(256), 0, st, (const mtb_kmer *)d_s, cnt, bits, rec);
-                STCHK(dev_sort(c, rec, cnt, 0, &d_s, nullptr, 0));
+                STCHK(dev_sort_groups(c, rec, cnt, bits, &d_s));
                 if (d_s != rec) HIPCHK(hipMemcpyAsync(rec, d_s, cnt * sizeof(mtb_kmer), hipMemcpyDeviceToDevice, st));
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(st));
@@ -4243,29 +4204,11 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
         HIPCHK(hipStreamSynchronize(st));
         S.ms_merge += (float)ms_since(t0);
         t0 = std::chrono::steady_clock::now();
-        uint32_t *d_head, *d_pos, *d_list; uint64_t *d_ws;
-        STCHK(ensure(c, "bhead", n, &d_head)); STCHK(ensure(c, "bpos", n + 1, &d_pos));
-        STCHK(ensure(c, "scanws", scan_ws_elems(n + 1), &d_ws));
-        hipLaunchKernelGGL(k_build_heads, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, d_head);
-        scan_launch<uint32_t, uint32_t, false>(st, d_head, n, true, d_pos, (uint32_t *)d_ws);
-        HIPCHK(hipGetLastError());
-        uint32_t n_groups = 0;
-        STCHK(d2h(c, &n_groups, d_pos + n, 4));
-        const uint64_t G = n_groups;
-        uint64_t *d_ov; uint32_t *d_oi;
-        STCHK(ensure(c, "mrgov", G + 1, &d_ov)); STCHK(ensure(c, "mrgoi", G + 1, &d_oi));
-        STCHK(ensure(c, "blist", n / (MTB_BUILD_LANE_MAX + 1) + 2, &d_list));
-        uint32_t *d_nlist = scal<uint32_t>(c, SC_JOIN_COUNT);
-        HIPCHK(scal_clear(c, SC_JOIN_COUNT));
-        hipLaunchKernelGGL(k_build_reduce, grid256(n), dim3(256), 0, st, (const mtb_kmer *)d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv, d_ov, d_oi, d_list, d_nlist);
-        HIPCHK(hipGetLastError());
-        uint32_t n_long = 0;
-        STCHK(d2h(c, &n_long, d_nlist, 4));
-        if (n_long) {
-            hipLaunchKernelGGL(k_build_reduce_long, dim3(std::min<uint32_t>(n_long, 1u << 16)), dim3(64), 0, st, (const mtb_kmer *)d_s, n, (const uint32_t *)d_head, (const uint32_t *)d_pos, tv,
-                               d_ov, d_oi, (const uint32_t *)d_list, (const uint32_t *)d_nlist);
-            HIPCHK(hipGetLastError());
-        }
+        uint64_t *d_ov = nullptr; uint32_t *d_oi = nullptr;
+        uint64_t G = 0; uint32_t n_long = 0;
+        STCHK(dev_reduce_groups(c, d_s, n, tv, [&](uint64_t groups, uint64_t **d_values, uint32_t **d_info) -> mtb_status {
+            STCHK(ensure(c, "mrgov", groups + 1, &d_ov)); STCHK(ensure(c, "mrgoi", groups + 1, &d_oi));
+            *d_values = d_ov; *d_info = d_oi; return MTB_OK; }, &G, &n_long));
         HIPCHK(hipStreamSynchronize(st));
         S.ms_reduce += (float)ms_since(t0);
         t0 = std::chrono::steady_clock::now();
@@ -4307,33 +4250,32 @@ mtb_status mtb_database_audit(mtb_ctx *c, const char *dbdir, const char *taxonom
     /* the taxonomy and species table of mtb_index_open, on the device: a holder index without targets */
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    mtb_index *hold = new mtb_index();
-    struct Guard { mtb_index *ix; ~Guard() { mtb_index_close(ix); } } guard{hold};
-    hold->ctx = c; hold->params = *params; hold->own = true;
+    mtbhost::Taxonomy tax;
     std::vector<int32_t> ids;
     {   const std::string taxdir = taxonomy_dir && *taxonomy_dir ? std::string(taxonomy_dir) : d + "/taxonomy";
-        const mtb_status s = load_database_taxonomy(d, taxdir, mtbhost::file_exists(d + "/taxonomyDB"), &hold->tax, &ids);
+        const mtb_status s = load_database_taxonomy(d, taxdir, mtbhost::file_exists(d + "/taxonomyDB"), &tax, &ids);
         if (s != MTB_OK) return failed(s); }
-    const uint64_t n_bins = (uint64_t)hold->tax.max_id + 1;
+    const uint64_t n_bins = (uint64_t)tax.max_id + 1;
     if (species_counts && cap < n_bins) {
         out->n_species = n_bins;
         return failed(fail(MTB_ERR_CAPACITY, "species_counts holds " + std::to_string(cap) + " entries, the taxonomy needs " + std::to_string(n_bins)));
     }
-    hold->info_mask = ~((uint32_t)(params->skip_redundancy == 0) << 31);
-    STCHK(upload_taxonomy(hold));
+    mtb_index *hold = nullptr;
+    STCHK(tax_holder_index(c, *params, std::move(tax), ids, &hold));
+    struct Guard { mtb_index *ix; ~Guard() { mtb_index_close(ix); } } guard{hold};
     const mtb_tax_view tv = tax_view(hold);
     /* chunk size: the caller's, else the decode's rule (128 M words, less under a workspace limit) within a 32nd of free HBM (a
      * chunk holds ~16 bytes per word on the device) */
     uint64_t CH = chunk_words;
     if (CH == 0) {
-        CH = 128ull << 20;
-        if (c->ws_limit) CH = std::max<uint64_t>(1u << 16, std::min<uint64_t>(CH, c->ws_limit / 16));
+        CH = decode_chunk_words(c);
         size_t fr = 0, tot = 0;
         HIPCHK(hipMemGetInfo(&fr, &tot));
         CH = std::max<uint64_t>(1u << 16, std::min<uint64_t>(CH, (fr + held_bytes(c, BUF_WORK)) / 32));
     }
     CH = std::max<uint64_t>(16, std::min<uint64_t>(CH, std::max<uint64_t>(R.n_words, 16)));
-    struct Scratch { mtb_ctx *c; ~Scratch() { for (const char *nm : {"auditv", "auditi", "auditbins", "auditlisted", "auditout", "auditcp", "diffraw", "difftc", "difftoff"}) release(c, nm); } } scratch{c};
+    struct Scratch { mtb_ctx *c; ~Scratch() { for (const char *nm : {"auditv", "auditi", "auditbins", "auditlisted", "auditout", "auditcp"}) release(c, nm); } } scratch{c};
+    DecodeScratch decode_scratch{c};
     uint64_t *d_v; uint32_t *d_i, *d_bins; uint8_t *d_listed; unsigned long long *d_out; mtb_audit_checkpoint *d_cp;
     const uint32_t CP_MAX = 4096;                                  /* checkpoints judged per launch */
     STCHK(ensure(c, "auditv", CH + 16, &d_v)); STCHK(ensure(c, "auditi", CH + 16, &d_i));
@@ -4386,10 +4328,9 @@ mtb_status mtb_database_audit(mtb_ctx *c, const char *dbdir, const char *taxonom
         HIPCHK(hipGetLastError());
         return MTB_OK;
     };
-    {   mtb_index tmp; tmp.ctx = c; tmp.params = *params; tmp.d_values = d_v; tmp.d_info = d_i;
-        OpenPlan P; P.n16 = R.n_words - R.n_trailing_words; P.T = R.n_info_entries; P.expect = UINT64_MAX;
-        bool dir_ok = false;
-        const mtb_status s = decode_chunked(c, &tmp, d, P, false, 1, false, &dir_ok, &sink);
+    {   mtbhost::MergeSlice whole;           /* every word before the trailing ones; how many entries they code is what the audit finds out */
+        whole.diff_hi = R.n_words - R.n_trailing_words; whole.info_hi = R.n_info_entries;
+        const mtb_status s = decode_chunked(c, params->kmer_format, d, whole, d_v, d_i, nullptr, &sink);
         if (s != MTB_OK) return failed(s); }
     /* checkpoints behind the last decoded word (among the trailing words) were never offered to a chunk */
     for (; next_cp < cps.size(); next_cp++) { missed_cp++; first_missed_cp = std::min(first_missed_cp, cps[next_cp].record); }

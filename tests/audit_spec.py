@@ -96,7 +96,7 @@ def taxonomy_tables(parent, rank, listed, aliases=None, max_id=None):
 
 # ---- the report ----------------------------------------------------------------------------------------------------------------------
 def usable_checkpoints(split, n_entries, n_words):
-    """record numbers of the split records a reader may start from (the rule of merge_input_from_split, host/merge_plan.h:43-53)"""
+    """record numbers of the split records a reader may start from (the rule of merge_input_from_split, host/merge_plan.h)"""
     out, last_info, last_aa, any_ = [], 0, 0, False
     for i in range(1, len(split)):
         ad, diff_off, info_off = (int(x) for x in split[i])
