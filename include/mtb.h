@@ -581,6 +581,45 @@ mtb_status mtb_merge_databases(mtb_ctx *, const char *const *dbdirs, uint32_t n_
  * (n_a + n_b records; equal records of a come first).  The tile of the merge kernel is 2048 records. */
 mtb_status mtb_merge_sorted(mtb_ctx *, const mtb_kmer *a, uint64_t n_a, const mtb_kmer *b, uint64_t n_b, mtb_kmer *out);
 
+/* ---- keep or drop clades while merging: a subset of a database, or "merge these, but without that clade" ------------------
+ * mtb_merge_databases with a filter on the species key right behind the keying of every slice (kernels_clade_filter.h: a stable
+ * compaction, two launches around a scan; host/clade_filter.h: the rule).  One input + a filter is a subset.  Everything said of
+ * mtb_merge_databases above holds: ranges, legacy inputs, slices built under another taxonomy, the dedup, the split table,
+ * db.parameters removed first and written last.
+ * Rule: the species key s of an entry is mtb_tax_species of its id under the taxonomy of `taxonomy_dir`.  s is KEPT iff (select is
+ * empty, or a selected taxon is s or an ancestor of s) and no excluded taxon is s or an ancestor of s.  Key 0 (ids without a
+ * species, e.g. root-labelled entries) is kept only when select is empty and the root is not excluded.  Ids are read after
+ * merged.dmp aliasing.
+ * Refusals, all MTB_ERR_ARG with nothing written, db.parameters already removed, the id named by mtb_last_error(): an id the taxonomy
+ * does not know; an id strictly below its own species key (a strain: it cannot be taken out of its species' LCA'd entries exactly,
+ * so it is refused, not approximated); both lists empty (use mtb_merge_databases); a selection that keeps no entry at all (found
+ * before the writer finishes: no openable empty database appears).  outdir equal to one of the inputs (realpaths are compared) is
+ * MTB_ERR_ARG as well, and the one refusal that comes before db.parameters is removed: the input stays the database it was.  An
+ * unknown id among the ENTRIES is an error as for mtb_merge_databases, also in a part the filter would drop.
+ * Contract: an entry's id is the LCA of its species' own records, so diffIdx, info, split, taxID_list and db.parameters are
+ * byte-identical to what the unfiltered merge writes once the entries of dropped species are removed from every input; for
+ * canonical inputs that is byte-identical to mtb_builder_add_records of only the kept species' records + mtb_builder_finish +
+ * mtb_index_write.  The result is the same for any max_range_records.
+ * Memory: within MTB_MERGE_BYTES_PER_RECORD (the range plan is made from the unfiltered counts, an upper bound): the kept records of
+ * a slice are compacted into the merge buffer that held the decoded slice and copied back, the per-tile counts lie where the dedup
+ * later keeps its head flags; keep[] and met[], one byte per taxonomy id each, come out of the fixed 4 GiB.
+ * fstats (may be NULL): keyed records before / after the filter over all inputs; distinct species keys met that were kept / dropped;
+ * listed taxa (select first, then exclude) under which no record was met -- a typo in an id shows here instead of passing as a
+ * silent no-op -- with the first of them (0 if none); host-clock ms of the filter (count, scan, compact, copy back; each slice ends
+ * with a stream synchronisation), which is part of stats->ms_read_decode. */
+typedef struct { const int32_t *select; uint32_t n_select; const int32_t *exclude; uint32_t n_exclude; } mtb_clade_filter;
+typedef struct { uint64_t n_records_in, n_records_kept;        /* keyed records before / after the filter, over all inputs */
+                 uint64_t n_species_kept, n_species_dropped;   /* distinct species keys met */
+                 uint32_t n_unmatched; int32_t first_unmatched; /* listed taxa under which no record was met; 0 if none */
+                 float ms_filter; } mtb_filter_stats;
+mtb_status mtb_merge_databases_filtered(mtb_ctx *, const char *const *dbdirs, uint32_t n_dbs, const char *taxonomy_dir,
+                                        const mtb_params *, const char *outdir, int split_num, uint64_t max_range_records,
+                                        const mtb_clade_filter *, mtb_merge_stats *stats, mtb_filter_stats *fstats /* both may be NULL */);
+/* stage call (parity seam), host arrays: the records whose (qinfo >> 32) indexes keep[] with a non-zero byte, in order, in `out`
+ * (room for n records); *n_out = how many.  A species key >= n_keep is MTB_ERR_ARG.  The kernels' tile is 2048 records. */
+mtb_status mtb_filter_records(mtb_ctx *, const mtb_kmer *rec, uint64_t n, const uint8_t *keep, uint64_t n_keep,
+                              mtb_kmer *out, uint64_t *n_out);
+
 /* ---- audit of a database directory ----
  * validateDatabase (validateDatabase.cpp:17-142: file presence, #end words of diffIdx == #info entries, "more robust validation will
  * be implemented in the future") extended to everything mtb_index_open, the joins and the readers that start at `split` checkpoints

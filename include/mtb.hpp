@@ -199,6 +199,18 @@ inline mtb_merge_stats mergeDatabases(mtb_ctx *ctx, const std::vector<std::strin
     check(mtb_merge_databases(ctx, dirs.data(), (uint32_t)dirs.size(), taxonomyDir.c_str(), &par, outDir.c_str(), splitNum, maxRangeRecords, &st));
     return st;
 }
+/* the same with a clade filter (mtb_merge_databases_filtered): only the entries of species under a selected taxon (all, if none is
+ * selected) and under no excluded one; filterStats (may be NULL) receives what the filter met */
+inline mtb_merge_stats mergeDatabases(mtb_ctx *ctx, const std::vector<std::string> &dbDirs, const std::string &taxonomyDir, const LocalParameters &par,
+                                      const std::string &outDir, const std::vector<int32_t> &selectTaxIds, const std::vector<int32_t> &excludeTaxIds,
+                                      int splitNum = 4096, uint64_t maxRangeRecords = 0, mtb_filter_stats *filterStats = nullptr) {
+    std::vector<const char *> dirs;
+    for (const std::string &d : dbDirs) dirs.push_back(d.c_str());
+    const mtb_clade_filter f = {selectTaxIds.data(), (uint32_t)selectTaxIds.size(), excludeTaxIds.data(), (uint32_t)excludeTaxIds.size()};
+    mtb_merge_stats st;
+    check(mtb_merge_databases_filtered(ctx, dirs.data(), (uint32_t)dirs.size(), taxonomyDir.c_str(), &par, outDir.c_str(), splitNum, maxRangeRecords, &f, &st, filterStats));
+    return st;
+}
 
 /* validateDatabase (validateDatabase.cpp:17-142) and the per-species entry counts of Classifier::countUniqueKmerPerSpecies
  * (Classifier.cpp:390-440) in one streaming pass: mtb_database_audit.  speciesCounts (may be NULL) is sized to the taxonomy here.

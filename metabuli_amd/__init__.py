@@ -235,14 +235,35 @@ class Context:
         _chk(self.L.mtb_builder_create(self.h, taxonomy_dir.encode(), C.byref(params), C.byref(h)))
         return Builder(self, h)
 
-    def merge_databases(self, dbdirs, taxonomy_dir, params, outdir, split_num=4096, max_range_records=0):
+    def merge_databases(self, dbdirs, taxonomy_dir, params, outdir, split_num=4096, max_range_records=0, select=None, exclude=None):
         """mtb_merge_databases: the databases `dbdirs` streamed into the existing directory `outdir`, one value range at a time (no
-        2^32-record limit, nothing re-sorted); max_range_records = 0 sizes the ranges from free HBM.  -> the call's statistics"""
+        2^32-record limit, nothing re-sorted); max_range_records = 0 sizes the ranges from free HBM.  -> the call's statistics.
+        select / exclude (lists of taxon ids at or above species rank; either given -> mtb_merge_databases_filtered): only the entries
+        of species under a selected taxon and under no excluded one are kept; the filter's statistics join the returned dict."""
         dirs = (C.c_char_p * max(len(dbdirs), 1))(*[d.encode() for d in dbdirs])
         s = MergeStats()
-        _chk(self.L.mtb_merge_databases(self.h, dirs, C.c_uint32(len(dbdirs)), taxonomy_dir.encode(), C.byref(params), outdir.encode(),
-                                        C.c_int(split_num), C.c_uint64(int(max_range_records)), C.byref(s)))
-        return {name: (float(getattr(s, name)) if name.startswith("ms_") else int(getattr(s, name))) for name, _ in MergeStats._fields_}
+        head = (self.h, dirs, C.c_uint32(len(dbdirs)), taxonomy_dir.encode(), C.byref(params), outdir.encode(), C.c_int(split_num), C.c_uint64(int(max_range_records)))
+        out = {}
+        if select is None and exclude is None:
+            _chk(self.L.mtb_merge_databases(*head, C.byref(s)))
+        else:
+            sel = np.ascontiguousarray([] if select is None else select, dtype=np.int32)
+            exc = np.ascontiguousarray([] if exclude is None else exclude, dtype=np.int32)
+            f = CladeFilter(sel.ctypes.data_as(C.POINTER(C.c_int32)), len(sel), exc.ctypes.data_as(C.POINTER(C.c_int32)), len(exc))
+            fs = FilterStats()
+            _chk(self.L.mtb_merge_databases_filtered(*head, C.byref(f), C.byref(s), C.byref(fs)))
+            out = {name: (float(getattr(fs, name)) if name.startswith("ms_") else int(getattr(fs, name))) for name, _ in FilterStats._fields_}
+        out.update({name: (float(getattr(s, name)) if name.startswith("ms_") else int(getattr(s, name))) for name, _ in MergeStats._fields_})
+        return out
+
+    def filter_records(self, rec, keep):
+        """mtb_filter_records (stage call of the clade filter's kernels): the records of the kmer_dt list `rec` whose species key
+        (qinfo >> 32) indexes the byte table `keep` with a non-zero byte, in order"""
+        rec = np.ascontiguousarray(rec, dtype=kmer_dt); keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        out = np.zeros(len(rec), kmer_dt)
+        n = C.c_uint64()
+        _chk(self.L.mtb_filter_records(self.h, _p(rec), C.c_uint64(len(rec)), _p(keep), C.c_uint64(len(keep)), _p(out), C.byref(n)))
+        return out[:n.value].copy()
 
     def audit_database(self, dbdir, taxonomy_dir=None, params=None, chunk_words=0, counts=True):
         """mtb_database_audit: one streaming pass over a database directory of any size -> (the report as a dict, the per-species entry
@@ -548,6 +569,17 @@ class MergeStats(C.Structure):
 
 
 MERGE_TILE = 2048          # records per tile of the merge kernel (MTB_MERGE_TILE, kernels_merge.h)
+
+
+class CladeFilter(C.Structure):
+    """mtb_clade_filter (include/mtb.h)"""
+    _fields_ = [("select", C.POINTER(C.c_int32)), ("n_select", C.c_uint32), ("exclude", C.POINTER(C.c_int32)), ("n_exclude", C.c_uint32)]
+
+
+class FilterStats(C.Structure):
+    """mtb_filter_stats (include/mtb.h)"""
+    _fields_ = [("n_records_in", C.c_uint64), ("n_records_kept", C.c_uint64), ("n_species_kept", C.c_uint64), ("n_species_dropped", C.c_uint64),
+                ("n_unmatched", C.c_uint32), ("first_unmatched", C.c_int32), ("ms_filter", C.c_float)]
 
 
 class AuditReport(C.Structure):

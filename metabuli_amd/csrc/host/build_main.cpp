@@ -23,7 +23,13 @@
  *
  *   mtb_build --audit 1 - - TAXONOMYDIR DBDIR      audit only (mtb_database_audit): the report is printed, DBDIR/sp2uniqKmerCnt (the
  *             reference's per-species entry counts, Classifier.cpp:390-440) is written, exit 1 if the database is not valid
- *   --validate-db 1 on any build, update or merge: OUTDB is audited after it is written; the run fails if it is not canonical */
+ *   --validate-db 1 on any build, update or merge: OUTDB is audited after it is written; the run fails if it is not canonical
+ *
+ *   mtb_build --add-db DB [--add-db DB2]... [--select-taxid A,B,..] [--exclude-taxid C,..] - - TAXONOMYDIR OUTDB
+ *             a subset of a database, or a merge without a clade (mtb_merge_databases_filtered; the flag names and the comma syntax
+ *             are classifiedRefiner's): only the entries of species under a selected taxon (all, if none is selected) and under no
+ *             excluded one are written.  Ids at or above species rank; legal for a pure merge only (GENOMES `-`), and always
+ *             streamed.  Prints the kept / dropped entries and species and one warning for listed ids under which nothing was met */
 #include <dirent.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -106,6 +112,20 @@ int main(int argc, char **argv) {
         std::vector<std::string> add_db, pos;
         bool audit_only = false, validate_db = false;
         std::string cds_list;
+        std::vector<int32_t> select_ids, exclude_ids;
+        bool filter_given = false;
+        auto id_list = [&](const std::string &flag, const std::string &v, std::vector<int32_t> *out) {      /* A,B,.. */
+            filter_given = true;
+            for (size_t at = 0; at <= v.size();) {
+                const size_t end = std::min(v.find(',', at), v.size());
+                const std::string tok = v.substr(at, end - at);
+                char *stop = nullptr;
+                const long id = strtol(tok.c_str(), &stop, 10);
+                if (tok.empty() || *stop || id < 0 || id > 0x7FFFFFFFl) die(flag + ": '" + tok + "' is not a taxon id (expected A,B,..)");
+                out->push_back((int32_t)id);
+                at = end + 1;
+            }
+        };
         int split_num = 4096, device = 0;
         unsigned long long max_records = 0;          /* 0: from the device */
         mtb_params par;
@@ -124,12 +144,15 @@ int main(int argc, char **argv) {
             else if (a == "--device") device = atoi(val().c_str());
             else if (a == "--audit") audit_only = atoi(val().c_str()) != 0;
             else if (a == "--validate-db") validate_db = atoi(val().c_str()) != 0;
+            else if (a == "--select-taxid") id_list(a, val(), &select_ids);
+            else if (a == "--exclude-taxid") id_list(a, val(), &exclude_ids);
             else if (a.size() > 2 && a.rfind("--", 0) == 0) die("unknown flag " + a);
             else pos.push_back(a);
         }
         if (pos.size() != 4) {
             fprintf(stderr, "usage: mtb_build [--add-db OLDDB]... [--cds-info LIST] [--max-records N] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d] "
-                            "[--validate-db 0|1] GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB\n       mtb_build --audit 1 [--device d] - - TAXONOMYDIR DBDIR\n");
+                            "[--validate-db 0|1] GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB\n       mtb_build --audit 1 [--device d] - - TAXONOMYDIR DBDIR\n"
+                            "       mtb_build --add-db DB [--add-db DB2]... [--select-taxid A,B,..] [--exclude-taxid C,..] - - TAXONOMYDIR OUTDB\n");
             return 1;
         }
         const std::string genomes = pos[0], map_path = pos[1], taxdir = pos[2], outdb = pos[3];
@@ -142,6 +165,8 @@ int main(int argc, char **argv) {
             return 0;
         }
         if (genomes == "-" && add_db.empty()) die("nothing to build: no genomes and no --add-db");
+        if (filter_given && genomes != "-")
+            die("--select-taxid / --exclude-taxid filter a merge of databases only (--add-db DB ... - - TAXONOMYDIR OUTDB): they cannot be combined with genomes on the command line");
         if (split_num < 2) die("--split-num must be at least 2");
         if (!cds_list.empty() && par.kmer_format != 2) die("--cds-info needs --kmer-format 2 (block extraction implements no other)");
 
@@ -256,6 +281,7 @@ int main(int argc, char **argv) {
         for (const std::string &db : add_db) n_old += entries_of(db);
         const bool streamed = genomes == "-" || !parts.empty() || mtb_builder_num_records(bld) + n_old > max_records;
         mtb_merge_stats ms = mtb_merge_stats();
+        mtb_filter_stats fs = mtb_filter_stats();
         if (!streamed) {
             for (const std::string &db : add_db) {
                 mtb_params q = par;
@@ -279,10 +305,20 @@ int main(int argc, char **argv) {
             std::vector<const char *> dirs;
             for (const std::string &p : parts) dirs.push_back(p.c_str());
             for (const std::string &db : add_db) { dirs.push_back(db.c_str()); fprintf(stderr, "mtb_build: %llu entries of %s\n", entries_of(db), db.c_str()); }
-            const mtb_status s = mtb_merge_databases(ctx, dirs.data(), (uint32_t)dirs.size(), taxdir.c_str(), &par, outdb.c_str(), split_num, max_given ? max_records : 0, &ms);
+            const mtb_clade_filter flt = {select_ids.data(), (uint32_t)select_ids.size(), exclude_ids.data(), (uint32_t)exclude_ids.size()};
+            const mtb_status s = filter_given
+                ? mtb_merge_databases_filtered(ctx, dirs.data(), (uint32_t)dirs.size(), taxdir.c_str(), &par, outdb.c_str(), split_num, max_given ? max_records : 0, &flt, &ms, &fs)
+                : mtb_merge_databases(ctx, dirs.data(), (uint32_t)dirs.size(), taxdir.c_str(), &par, outdb.c_str(), split_num, max_given ? max_records : 0, &ms);
             const std::string err = s == MTB_OK ? std::string() : std::string(mtb_last_error());
             remove_tree(parts_dir);
-            if (s != MTB_OK) die("mtb_merge_databases: " + err);
+            if (s != MTB_OK) die(std::string(filter_given ? "mtb_merge_databases_filtered: " : "mtb_merge_databases: ") + err);
+            if (filter_given) {
+                fprintf(stderr, "mtb_build: filter kept %llu of %llu entries (%llu dropped), %llu of %llu species (%llu dropped), %.1f ms\n",
+                        (unsigned long long)fs.n_records_kept, (unsigned long long)fs.n_records_in, (unsigned long long)(fs.n_records_in - fs.n_records_kept),
+                        (unsigned long long)fs.n_species_kept, (unsigned long long)(fs.n_species_kept + fs.n_species_dropped), (unsigned long long)fs.n_species_dropped, fs.ms_filter);
+                if (fs.n_unmatched) fprintf(stderr, "mtb_build: warning: no entry of the inputs lies under taxon %d\n", fs.first_unmatched);
+                if (fs.n_unmatched > 1) fprintf(stderr, "mtb_build: warning: ... nor under %u further listed taxa\n", fs.n_unmatched - 1);
+            }
             n_entries = ms.n_entries;
         }
         const std::string otax = outdb + "/taxonomy";

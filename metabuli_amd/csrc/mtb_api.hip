@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
+#include <limits.h>
+#include <stdlib.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -21,12 +23,14 @@
 #include "host_db.h"
 #include "host/merge_plan.h"
 #include "host/audit_plan.h"
+#include "host/clade_filter.h"
 #include "kernels_extract.h"
 #include "kernels_extract_blocks.h"
 #include "kernels_index.h"
 #include "kernels_join.h"
 #include "kernels_build.h"
 #include "kernels_merge.h"
+#include "kernels_clade_filter.h"
 #include "kernels_audit.h"
 #include "kernels_dir.h"
 #include "kernels_scan.h"
@@ -4060,9 +4064,55 @@ static mtb_status dev_merge_tree(mtb_ctx *c, mtb_kmer *ping, mtb_kmer *pong, std
 namespace {
 struct MergeSource { std::string dir; uint32_t info_mask = 0xFFFFFFFFu; };
 double ms_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+/* the device side of a clade filter: keep[] and met[] by species key, and the per-tile counts, bases and scan workspace */
+struct CladeDev { const uint8_t *d_keep = nullptr; uint64_t n_keep = 0; uint8_t *d_met = nullptr; uint32_t *d_count = nullptr; uint64_t *d_base = nullptr, *d_ws = nullptr; };
+}
+
+/* out[0, *kept) = the records of rec[0, n) whose species key indexes keep[] with a non-zero byte, in order (device pointers; out
+ * holds n records and does not overlap rec; f.d_count / d_base / d_ws hold n / 2048 + 1, + 2 and scan_ws_elems(n / 2048 + 2) entries).
+ * *first_bad = the first record whose key is >= n_keep, ~0 if none.  Ends with the download of the count: the stream is idle. */
+static mtb_status dev_clade_filter(mtb_ctx *c, const mtb_kmer *rec, uint64_t n, const CladeDev &f, mtb_kmer *out, uint64_t *kept, uint64_t *first_bad) {
+    *kept = 0; *first_bad = ~0ull;
+    if (n == 0) return MTB_OK;
+    hipStream_t st = c->stream;
+    const uint64_t n_tiles = (n + MTB_CLADE_TILE - 1) / MTB_CLADE_TILE;
+    unsigned long long *d_bad = scal<unsigned long long>(c, SC_JOIN_COUNT);
+    HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, st));
+    hipLaunchKernelGGL(k_clade_count, dim3((uint32_t)n_tiles), dim3(MTB_CLADE_THREADS), 0, st, rec, n, f.d_keep, f.n_keep, f.d_met, f.d_count, d_bad);
+    scan_launch<uint32_t, uint64_t, false>(st, (const uint32_t *)f.d_count, n_tiles, true, f.d_base, f.d_ws);
+    hipLaunchKernelGGL(k_clade_compact, dim3((uint32_t)n_tiles), dim3(MTB_CLADE_THREADS), 0, st, rec, n, f.d_keep, f.n_keep, (const uint64_t *)f.d_base, out);
+    HIPCHK(hipGetLastError());
+    unsigned long long bad = 0;
+    STCHK(d2h(c, kept, f.d_base + n_tiles, 8));
+    STCHK(d2h(c, &bad, d_bad, 8));
+    *first_bad = bad;
+    return MTB_OK;
 }
 
 extern "C" {
+
+mtb_status mtb_filter_records(mtb_ctx *c, const mtb_kmer *rec, uint64_t n, const uint8_t *keep, uint64_t n_keep, mtb_kmer *out, uint64_t *n_out) {
+    if (!c || !n_out || (n && (!rec || !out)) || (n_keep && !keep)) return fail(MTB_ERR_ARG, "NULL argument");
+    *n_out = 0;
+    if (n == 0) return MTB_OK;
+    if (n >> 32) return fail(MTB_ERR_ARG, "2^32 or more records in one call");
+    HIPCHK(hipSetDevice(c->device));
+    const uint64_t n_tiles = (n + MTB_CLADE_TILE - 1) / MTB_CLADE_TILE;
+    mtb_kmer *d_in, *d_out; uint8_t *d_keep; CladeDev f;
+    STCHK(ensure(c, "mrgA", n, &d_in)); STCHK(ensure(c, "mrgB", n, &d_out));
+    STCHK(ensure(c, "cladekeep", n_keep + 1, &d_keep));
+    STCHK(ensure(c, "bhead", n_tiles + 1, &f.d_count)); STCHK(ensure(c, "bpos", n_tiles + 2, &f.d_base));
+    STCHK(ensure(c, "scanws", scan_ws_elems(n_tiles + 2), &f.d_ws));
+    STCHK(h2d(c, d_in, rec, n * sizeof(mtb_kmer)));
+    if (n_keep) STCHK(h2d(c, d_keep, keep, n_keep));
+    f.d_keep = d_keep; f.n_keep = n_keep;
+    uint64_t kept = 0, bad = 0;
+    STCHK(dev_clade_filter(c, d_in, n, f, d_out, &kept, &bad));
+    if (bad != ~0ull) return fail(MTB_ERR_ARG, "record " + std::to_string(bad) + " has species key " + std::to_string(rec[bad].qinfo >> 32) + ", keep[] holds " + std::to_string(n_keep) + " entries");
+    if (kept) STCHK(d2h(c, out, d_out, kept * sizeof(mtb_kmer)));
+    *n_out = kept;
+    return MTB_OK;
+}
 
 mtb_status mtb_merge_sorted(mtb_ctx *c, const mtb_kmer *a, uint64_t n_a, const mtb_kmer *b, uint64_t n_b, mtb_kmer *out) {
     if (!c || (n_a && !a) || (n_b && !b) || ((n_a + n_b) && !out)) return fail(MTB_ERR_ARG, "NULL argument");
@@ -4077,11 +4127,23 @@ mtb_status mtb_merge_sorted(mtb_ctx *c, const mtb_kmer *a, uint64_t n_a, const m
     return MTB_OK;
 }
 
-mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n_dbs, const char *taxonomy_dir, const mtb_params *params,
-                               const char *outdir, int split_num, uint64_t max_range_records, mtb_merge_stats *stats) {
+/* mtb_merge_databases (flt == NULL) and mtb_merge_databases_filtered: one body */
+static mtb_status merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n_dbs, const char *taxonomy_dir, const mtb_params *params,
+                                  const char *outdir, int split_num, uint64_t max_range_records, const mtb_clade_filter *flt, mtb_merge_stats *stats,
+                                  mtb_filter_stats *fstats) {
     if (!c || !taxonomy_dir || !params || !outdir || split_num < 2) return fail(MTB_ERR_ARG, "NULL argument / split_num < 2");
+    if (flt && dbdirs) {
+        /* a subset written over its own input would read what it has already overwritten: refused before anything in outdir is
+         * touched, so the input stays the database it was */
+        char ro[PATH_MAX], ri[PATH_MAX];
+        if (realpath(outdir, ro))
+            for (uint32_t i = 0; i < n_dbs; i++)
+                if (dbdirs[i] && realpath(dbdirs[i], ri) && !strcmp(ro, ri)) return fail(MTB_ERR_ARG, std::string("the output directory is the input ") + dbdirs[i] + ": a filtered merge does not write over what it reads");
+    }
     unlink((std::string(outdir) + "/db.parameters").c_str());          /* whatever happens below: no half-written database that opens */
     if (n_dbs == 0 || !dbdirs) return fail(MTB_ERR_ARG, "no databases to merge");
+    mtb_filter_stats F; memset(&F, 0, sizeof(F));
+    if (flt && flt->n_select + (uint64_t)flt->n_exclude == 0) return fail(MTB_ERR_ARG, "neither a selected nor an excluded taxon: nothing to filter (use mtb_merge_databases)");
     if (params->kmer_format != 1 && params->kmer_format != 2) return fail(MTB_ERR_UNSUPPORTED, "only kmer_format 1 and 2 are implemented");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->stream;
@@ -4126,6 +4188,20 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
     struct Guard { mtb_index *ix; ~Guard() { mtb_index_close(ix); } } guard{hold};
     const mtb_tax_view tv = tax_view(hold);
     const int bits = mtb_build_tax_bits(hold->tax.max_id);
+    /* the filter: keep[] by species key from the host (host/clade_filter.h), uploaded once; met[] is cleared here and read at the end */
+    struct FilterScratch { mtb_ctx *c; ~FilterScratch() { release(c, "cladekeep"); release(c, "clademet"); } } filter_scratch{c};
+    mtbhost::CladeFilter cf;
+    CladeDev fd;
+    if (flt) {
+        std::string err;
+        if (!mtbhost::clade_filter_make(hold->tax, flt->select, flt->n_select, flt->exclude, flt->n_exclude, &cf, &err)) return fail(MTB_ERR_ARG, err);
+        uint8_t *d_keep;
+        fd.n_keep = cf.keep.size();
+        STCHK(ensure(c, "cladekeep", cf.keep.size(), &d_keep)); STCHK(ensure(c, "clademet", cf.keep.size(), &fd.d_met));
+        STCHK(h2d(c, d_keep, cf.keep.data(), cf.keep.size()));
+        HIPCHK(hipMemsetAsync(fd.d_met, 0, cf.keep.size(), st));
+        fd.d_keep = d_keep;
+    }
     /* the ranges */
     uint64_t budget = max_range_records;
     if (budget == 0) {
@@ -4155,6 +4231,14 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
         if (R.records == 0) continue;
         mtb_kmer *d_a, *d_b;
         STCHK(ensure(c, "mrgA", R.records + 1, &d_a)); STCHK(ensure(c, "mrgB", R.records + 1, &d_b));
+        if (flt) {
+            /* tile counts and bases lie where the reduce keeps its head flags and positions, unused until then (asked for at the size
+             * the reduce asks for at most, so that it does not allocate them again) */
+            const uint64_t tiles = R.records / MTB_CLADE_TILE + 1;
+            STCHK(ensure(c, "bhead", std::max<uint64_t>(R.records, tiles + 1), &fd.d_count));
+            STCHK(ensure(c, "bpos", std::max<uint64_t>((R.records + 1) / 2 + 1, tiles + 2), &fd.d_base));
+            STCHK(ensure(c, "scanws", scan_ws_elems(R.records + 1), &fd.d_ws));
+        }
         std::vector<uint64_t> off(1, 0);
         auto t0 = std::chrono::steady_clock::now();
         for (uint32_t i = 0; i < n_dbs; i++) {
@@ -4168,7 +4252,7 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
             HIPCHK(hipGetLastError());
             uint64_t ab[2] = {0, 0};
             STCHK(d2h(c, ab, d_trim, 16));
-            const uint64_t cnt = ab[1] - ab[0];
+            uint64_t cnt = ab[1] - ab[0];
             if (cnt == 0) continue;
             mtb_kmer *rec = d_a + off.back();
             HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, st)); HIPCHK(hipMemsetAsync(d_unsorted, 0, 8, st));
@@ -4182,6 +4266,18 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
                 STCHK(d2h(c, &r, rec + flags[0], sizeof(r)));
                 return fail(MTB_ERR_ARG, "taxid " + std::to_string(mtb_build_key_taxid(r.qinfo)) + " of " + src[i].dir + " (entry " + std::to_string(sl.info_lo + ab[0] + flags[0]) +
                                          ") is not in the merge's taxonomy");
+            }
+            if (flt) {
+                /* the decoded slice in d_b is dead: the kept records are compacted into it and copied back */
+                const auto tf = std::chrono::steady_clock::now();
+                uint64_t kept = 0, bad = 0;
+                STCHK(dev_clade_filter(c, rec, cnt, fd, d_b, &kept, &bad));
+                if (bad != ~0ull) return fail(MTB_ERR_DEVICE, "a species key of " + src[i].dir + " lies outside the taxonomy (internal error)");
+                if (kept && kept != cnt) { HIPCHK(hipMemcpyAsync(rec, d_b, kept * sizeof(mtb_kmer), hipMemcpyDeviceToDevice, st)); HIPCHK(hipStreamSynchronize(st)); }
+                F.ms_filter += (float)ms_since(tf);
+                F.n_records_in += cnt; F.n_records_kept += kept;
+                cnt = kept;
+                if (cnt == 0) continue;
             }
             if ((uint32_t)flags[1]) {
                 /* built under another taxonomy: not ascending under this one -- the builder's two radix sorts, for this slice alone */
@@ -4216,12 +4312,33 @@ mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n
         S.ms_encode_write += (float)ms_since(t0);
         S.n_entries += G;
     }
+    if (flt) {
+        /* before the writer finishes: a selection that keeps nothing leaves no database behind, not an empty one that opens */
+        if (F.n_records_kept == 0) return fail(MTB_ERR_ARG, "the selection keeps none of the " + std::to_string(F.n_records_in) + " entries: nothing written");
+        std::vector<uint8_t> met(cf.keep.size());
+        STCHK(d2h(c, met.data(), fd.d_met, met.size()));
+        const mtbhost::CladeFilterCounts k = mtbhost::clade_filter_counts(hold->tax, cf, met.data());
+        F.n_species_kept = k.n_species_kept; F.n_species_dropped = k.n_species_dropped; F.n_unmatched = k.n_unmatched; F.first_unmatched = k.first_unmatched;
+    }
     auto t0 = std::chrono::steady_clock::now();
     STCHK(w.finish(split_num));
     S.ms_split = (float)ms_since(t0);
     S.ms_total = (float)ms_since(t_all);
     if (stats) *stats = S;
+    if (fstats) *fstats = F;
     return MTB_OK;
+}
+
+mtb_status mtb_merge_databases(mtb_ctx *c, const char *const *dbdirs, uint32_t n_dbs, const char *taxonomy_dir, const mtb_params *params,
+                               const char *outdir, int split_num, uint64_t max_range_records, mtb_merge_stats *stats) {
+    return merge_databases(c, dbdirs, n_dbs, taxonomy_dir, params, outdir, split_num, max_range_records, nullptr, stats, nullptr);
+}
+
+mtb_status mtb_merge_databases_filtered(mtb_ctx *c, const char *const *dbdirs, uint32_t n_dbs, const char *taxonomy_dir, const mtb_params *params,
+                                        const char *outdir, int split_num, uint64_t max_range_records, const mtb_clade_filter *filter, mtb_merge_stats *stats,
+                                        mtb_filter_stats *fstats) {
+    if (!filter) { if (outdir) unlink((std::string(outdir) + "/db.parameters").c_str()); return fail(MTB_ERR_ARG, "NULL filter (use mtb_merge_databases)"); }
+    return merge_databases(c, dbdirs, n_dbs, taxonomy_dir, params, outdir, split_num, max_range_records, filter, stats, fstats);
 }
 
 /* ---- audit of a database directory (mtb.h; kernels_audit.h, host/audit_plan.h) ---- */
