@@ -666,6 +666,44 @@ mtb_status mtb_database_audit(mtb_ctx *, const char *dbdir, const char *taxonomy
 /* DBDIR/sp2uniqKmerCnt as Classifier.cpp:433-437 writes it: one "<id> <count>\n" per non-zero count, ids ascending */
 mtb_status mtb_audit_write_species_counts(const char *dbdir, const uint32_t *species_counts, uint64_t n);
 
+/* ---- k-mer coverage: which database entries the classified reads touched ----------------------------------------------------
+ * KrakenUniq's question, per species: how many distinct database k-mers did the reads hit, how often, and what share of the
+ * species' k-mers is that -- 5 000 reads on the same 200 metamers of one conserved gene read differently from a genome sampled
+ * evenly.  No reference counterpart (sp2uniqKmerCnt, Classifier.cpp:390-440, is the denominator only).  The rule is stated once,
+ * in tests/coverage_spec.py; in short: a query metamer of a read classified at or below a species s marks every entry with the
+ * same 64-bit value whose id has species s, and counts one hit for s if there is such an entry.
+ * The state belongs to the INDEX (several contexts, lanes and sub-batches classify against one): a bitmap of one bit per entry
+ * position -- ceil(T / 32) u32 words: 2 GB at T = 16 G -- and u64 `hits` bins, one per taxonomy id.  Off by default: no kernel, no byte.
+ *   begin   allocates and clears both.  MTB_ERR_ARG when coverage is already on; MTB_ERR_UNSUPPORTED for a view (mtb_index_slice)
+ *           or a part (mtb_index_open_part); MTB_ERR_OOM leaves the index as it was.
+ *   end     frees both (mtb_index_close does it too).  MTB_ERR_ARG when coverage is off.
+ *   While coverage is on, every single-index classify call (mtb_classify_batch, _device, _packed, _packed_async, with any number of
+ *   streams or sub-batches) marks and counts, behind the scoring of each read range: ms_score and ms_total include it.
+ *   mtb_classify_batch_partitioned does not (parts cannot begin).  Hits are counted exactly once per call that returned MTB_OK
+ *   and not at all for a call that returned an error (a context keeps the hits of the call in work apart and commits them at its
+ *   successful end); the bitmap is idempotent and a failed call may leave the marks of the read ranges it finished -- the caller
+ *   repeats the batch, which sets the same bits.  The index is never converted: the array is read flat or packed, as it is;
+ *   mtb_index_seal, packing and unpacking keep positions, so the bitmap survives them.  A clone of an index with coverage on
+ *   starts with coverage off.  begin / end / merge must not run while a classify call against the index is in flight.
+ *   merge   dst.marked |= src.marked, dst.hits += src.hits (counters too), for two indices with equal T and taxonomy -- a clone and
+ *           its source, on one device or two; the bitmap crosses through a staging buffer of at most 64 MiB.  src is unchanged.
+ *           MTB_ERR_ARG: different sizes, the same index twice, or coverage off on either side.
+ *   report  distinct[s], hits[s], total[s] (host; each may be NULL; cap entries each, at least mtb_tax_max_id + 1, else
+ *           MTB_ERR_CAPACITY as for mtb_database_audit): one streaming pass over the resident array.  total[s] equals
+ *           mtb_database_audit's species_counts[s] for s != 0.  Nothing is cleared; it may be called repeatedly.  The CALLER has
+ *           synchronised every context that classified against the index (classify calls that have returned are complete).
+ *           stats (may be NULL): entries, set bits, the sum of hits, query records seen (blanks excluded) and those of reads with
+ *           a species, committed calls, device ms of the pass.
+ *   mark    the stage call (parity seam), host arrays: the metamers `kmers` (any order, blanks allowed) of reads whose outcomes
+ *           are results[0, n_reads) (sequenceID 1..n_reads), through the same device code as the fused path; counts as one call.
+ *           A sequenceID beyond n_reads is MTB_ERR_ARG, found on the host before anything is launched. */
+typedef struct { uint64_t n_targets, n_marked, n_hits, n_queries, n_queries_counted, n_batches; float ms_count; } mtb_coverage_stats;
+mtb_status mtb_index_coverage_begin(mtb_index *);
+mtb_status mtb_index_coverage_end(mtb_index *);
+mtb_status mtb_index_coverage_merge(mtb_index *dst, mtb_index *src);
+mtb_status mtb_index_coverage_report(mtb_index *, uint64_t *distinct, uint64_t *hits, uint64_t *total, uint64_t cap, mtb_coverage_stats *);
+mtb_status mtb_index_coverage_mark(mtb_ctx *, mtb_index *, const mtb_kmer *kmers, uint64_t n, const mtb_result *results, uint64_t n_reads);
+
 #ifdef __cplusplus
 }
 #endif

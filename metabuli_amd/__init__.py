@@ -355,6 +355,12 @@ class Context:
                               C.c_uint64(n_reads), _p(qlen), _p(qlen2), _p(res), _p(tt), _p(tc), C.c_uint64(cap), C.byref(n)))
         return compact_taxcnt(res, tt, tc)
 
+    def coverage_mark(self, index, kmers, results):
+        """mtb_index_coverage_mark (stage call of the coverage kernels): the kmer_dt list `kmers` (any order, blanks allowed) of the
+        reads whose outcomes are the result_dt rows `results` marks and counts against `index` (coverage on), as one call"""
+        k = np.ascontiguousarray(kmers, dtype=kmer_dt); r = np.ascontiguousarray(results, dtype=result_dt)
+        _chk(self.L.mtb_index_coverage_mark(self.h, index.h, _p(k), C.c_uint64(len(k)), _p(r), C.c_uint64(len(r))))
+
     # ---- fused batch ----
     def classify_batch(self, index, params, bases, offs, bases2=None, offs2=None, taxcnt_cap=None):
         """taxcnt_cap: capacity of the host arrays for the packed taxID:count lists (default: ample); too small -> the call is
@@ -659,6 +665,10 @@ class Builder:
             self.h = None
 
 
+class CoverageStats(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("n_targets", "n_marked", "n_hits", "n_queries", "n_queries_counted", "n_batches")] + [("ms_count", C.c_float)]
+
+
 class Index:
     def __init__(self, ctx, h):
         self.ctx = ctx
@@ -693,6 +703,31 @@ class Index:
     def original_id(self, taxid):
         """TaxonomyWrapper::getOriginalTaxID: internal id (what results carry) -> the id the reports print"""
         return int(self.ctx.L.mtb_tax_original_id(self.h, C.c_int32(int(taxid))))
+
+    def max_taxid(self):
+        return int(self.ctx.L.mtb_tax_max_id(self.h))
+
+    def coverage_begin(self):
+        """mtb_index_coverage_begin: from here on every classify call against this index marks the database entries its reads touched"""
+        _chk(self.ctx.L.mtb_index_coverage_begin(self.h))
+
+    def coverage_end(self):
+        _chk(self.ctx.L.mtb_index_coverage_end(self.h))
+
+    def coverage_merge(self, other):
+        """mtb_index_coverage_merge: this index's marks |= other's, hits += other's (a clone and its source)"""
+        _chk(self.ctx.L.mtb_index_coverage_merge(self.h, other.h))
+
+    def coverage_report(self, cap=None):
+        """mtb_index_coverage_report -> dict: `distinct`, `hits`, `total` (uint64 arrays indexed by species id, max id + 1 entries)
+        and the fields of mtb_coverage_stats.  Nothing is cleared.  cap: the arrays' size, to see the refusal of a small one."""
+        n = self.max_taxid() + 1 if cap is None else int(cap)
+        d = np.zeros(n, np.uint64); h = np.zeros(n, np.uint64); t = np.zeros(n, np.uint64)
+        st = CoverageStats()
+        _chk(self.ctx.L.mtb_index_coverage_report(self.h, _p(d), _p(h), _p(t), C.c_uint64(n), C.byref(st)))
+        out = {name: (float(getattr(st, name)) if name.startswith("ms_") else int(getattr(st, name))) for name, _ in CoverageStats._fields_}
+        out.update(distinct=d, hits=h, total=t)
+        return out
 
     def slice(self, lo_value, hi_value, is_last):
         """device view of the value range [lo, hi) (mtb_index_slice); close it before the parent"""

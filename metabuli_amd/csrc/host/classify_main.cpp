@@ -20,6 +20,9 @@
  *          --print-log, -v   (LocalParameters.cpp:631-654).  Refused: --mask 1, --reduced-aa 1 (they change the answers)
  *   --validate-db 1: the database is audited before it is opened (mtb_database_audit: validateDatabase.cpp's file and count checks,
  *          value order, ids against the taxonomy, every split checkpoint); exit 1 with "Database validation failed." if it is not valid
+ *   --kmer-coverage 0|1 (default 0): KrakenUniq's figures per species -- the distinct database k-mers the reads of that species touched, how often,
+ *          and what share of the species' k-mers that is (mtb_index_coverage_*; the rule: tests/coverage_spec.py) -- as <OUTDIR>/<JobID>_kmer_coverage.tsv,
+ *          one row per species with reads, ascending by the printed id.  Not with --partitioned 1 or --filter 1.  No other output changes.
  *   filter mode (`metabuli filter`, src/workflow/filter.cpp:5-45, QueryFilter.cpp:75-186): --filter 1 [--print-mode 1|2] <FASTA/Q> [<mate>] <DBDIR>
  *          classifies with the filter command's defaults (--min-score 0.5 unless given) and writes, next to the input,
  *          <base>_filtered.fna (reads NOT classified = not contamination), with --print-mode 2 also <base>_removed.fna (classified
@@ -269,6 +272,10 @@ void write_krona(FILE *fp, const CladeTable &ct, unsigned long total) {
 /* An engine that implements the classification part of the C ABI alone (a stand-in library linked in place of libmtb.so) need not
  * have the audit: the reference is weak, and --validate-db 1 is refused where it is absent. */
 extern "C" mtb_status mtb_database_audit(mtb_ctx *, const char *, const char *, mtb_params *, uint64_t, uint32_t *, uint64_t, mtb_audit_report *) __attribute__((weak));
+/* ... nor the k-mer coverage: --kmer-coverage 1 is refused where it is absent */
+extern "C" mtb_status mtb_index_coverage_begin(mtb_index *) __attribute__((weak));
+extern "C" mtb_status mtb_index_coverage_merge(mtb_index *, mtb_index *) __attribute__((weak));
+extern "C" mtb_status mtb_index_coverage_report(mtb_index *, uint64_t *, uint64_t *, uint64_t *, uint64_t, mtb_coverage_stats *) __attribute__((weak));
 namespace {
 bool validate_database(const std::string &dbdir, const std::string &taxdir, mtb_params par, int device) {
     printf("Validating database: %s\n", dbdir.c_str());
@@ -313,7 +320,7 @@ int main(int argc, char **argv) {
     int threads = (int)std::max(1u, std::min(128u, std::thread::hardware_concurrency()));
     bool lineage = false, filter = false, min_score_given = false, partitioned = false, pack = true, async_results = false; int print_mode = 1, gpu_workers = 1;
     std::vector<std::string> pos;
-    bool validate_db = false;
+    bool validate_db = false, kmer_coverage = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() { if (i + 1 >= argc) { fprintf(stderr, "missing value for %s\n", a.c_str()); exit(1); } return std::string(argv[++i]); };
@@ -335,6 +342,7 @@ int main(int argc, char **argv) {
         else if (a == "--partitioned") partitioned = atoi(val().c_str()) != 0;
         else if (a == "--pack-reads") pack = atoi(val().c_str()) != 0;
         else if (a == "--async-results") async_results = atoi(val().c_str()) != 0;
+        else if (a == "--kmer-coverage") kmer_coverage = atoi(val().c_str()) != 0;
         else if (a == "--gpu-workers") gpu_workers = std::max(1, std::min(4, atoi(val().c_str())));
         else if (a == "--devices") { devices.clear(); std::stringstream ss(val()); std::string tok; while (std::getline(ss, tok, ',')) if (!tok.empty()) devices.push_back(atoi(tok.c_str())); }
         else if (a == "--reduced-aa") { if (atoi(val().c_str()) != 0) { fprintf(stderr, "mtb_classify: --reduced-aa 1 is not implemented\n"); return 1; } }
@@ -351,6 +359,8 @@ int main(int argc, char **argv) {
         else if (a.rfind("--", 0) == 0) { fprintf(stderr, "mtb_classify: unknown flag %s\n", a.c_str()); return 1; }
         else pos.push_back(a);
     }
+    if (kmer_coverage && (partitioned || filter)) { fprintf(stderr, "mtb_classify: --kmer-coverage 1 cannot be combined with --partitioned 1 or --filter 1\n"); return 1; }
+    if (kmer_coverage && !(mtb_index_coverage_begin && mtb_index_coverage_merge && mtb_index_coverage_report)) { fprintf(stderr, "mtb_classify: --kmer-coverage 1: this engine has no k-mer coverage support\n"); return 1; }
     const bool paired = par.seq_mode == 2;
     size_t need = (paired ? 5 : 4) - (filter ? 2 : 0);
     if (pos.size() != need) {
@@ -459,6 +469,8 @@ int main(int argc, char **argv) {
             fprintf(stderr, "mtb_classify: resident index cloned to %zu more device(s) concurrently in %.2f s (%.1f GB each, %.1f GB/s aggregate)\n",
                     devices.size() - 1, tc, gb, gb * (double)(devices.size() - 1) / std::max(tc, 1e-9));
         }
+        /* --kmer-coverage 1: every engine's copy of the index collects the marks of its share of the reads */
+        if (kmer_coverage) for (auto &e : engs) mtb::check(mtb_index_coverage_begin(e->index));
         } catch (const std::exception &e) {                   /* (the parser thread is running: leave at once) */
             fprintf(stderr, "mtb_classify: %s\n", e.what()); fflush(stderr); _exit(1);
         }
@@ -697,6 +709,29 @@ int main(int argc, char **argv) {
         if (!fp) throw std::runtime_error("cannot write the report");
         write_report(fp, ct, total);
         fclose(fp);
+        if (kmer_coverage) {
+            /* the engines' marks and hits united in engine 0, one pass over its array, one row per species with reads (the row format: tests/coverage_spec.py) */
+            for (size_t d = 1; d < ND; d++) mtb::check(mtb_index_coverage_merge(eng.index, engs[d]->index));
+            const size_t n_ids = (size_t)mtb_tax_max_id(eng.index) + 1;
+            std::vector<uint64_t> distinct(n_ids, 0), hits(n_ids, 0), db(n_ids, 0), reads(n_ids, 0);
+            mtb::check(mtb_index_coverage_report(eng.index, distinct.data(), hits.data(), db.data(), n_ids, nullptr));
+            for (size_t t = 1; t < n_ids && t < tax_counts.size(); t++) {
+                const int32_t s = tax_counts[t] ? mtb_tax_species(eng.index, (int32_t)t) : 0;
+                if (s > 0 && (size_t)s < n_ids) reads[(size_t)s] += tax_counts[t];
+            }
+            std::vector<std::pair<int32_t, int32_t>> rows;        /* (printed id, species) */
+            for (size_t s = 1; s < n_ids; s++) if (reads[s]) rows.emplace_back(mtb_tax_original_id(eng.index, (int32_t)s), (int32_t)s);
+            std::sort(rows.begin(), rows.end());
+            fp = fopen((prefix + "_kmer_coverage.tsv").c_str(), "w");
+            if (!fp) throw std::runtime_error("cannot write the k-mer coverage file");
+            fprintf(fp, "#taxID\tname\treads\tkmer_hits\tdistinct_kmers\tdb_kmers\tcoverage\tduplication\n");
+            for (const auto &r : rows) {
+                const size_t s = (size_t)r.second;
+                fprintf(fp, "%d\t%s\t%llu\t%llu\t%llu\t%llu\t%.6f\t%.3f\n", r.first, mtb_tax_name(eng.index, r.second), (unsigned long long)reads[s], (unsigned long long)hits[s],
+                        (unsigned long long)distinct[s], (unsigned long long)db[s], db[s] ? (double)distinct[s] / (double)db[s] : 0.0, distinct[s] ? (double)hits[s] / (double)distinct[s] : 0.0);
+            }
+            fclose(fp);
+        }
         if (!filter) {                                        /* the filter command writes the default report only (QueryFilter.cpp:198) */
             fp = fopen((prefix + "_krona.html").c_str(), "w");
             if (!fp) throw std::runtime_error("cannot write the krona file");

@@ -32,6 +32,7 @@
 #include "kernels_merge.h"
 #include "kernels_clade_filter.h"
 #include "kernels_audit.h"
+#include "kernels_coverage.h"
 #include "kernels_dir.h"
 #include "kernels_scan.h"
 #include "kernels_score.h"
@@ -177,6 +178,9 @@ struct mtb_ctx {
     struct JoinTune { uint64_t key = 0; int calls = 0, pending = -1, best = -1; float ms[3] = {0.0f, 0.0f, 0.0f}; hipEvent_t e0 = nullptr, e1 = nullptr; } join_tunes[4]; uint32_t join_tune_next = 0;      /* dev_join: the short-read instantiation that is fastest for this index and batch size */
     uint64_t many_stats[4] = {0, 0, 0, 0};           /* last slot-path batch: reads deferred by the first scoring launches, of those scored by k_score_many, their matches, the survivors of the dead-species drop */
     uint32_t lslot_tf_start = 1;                     /* long-read slot ranges: tail factor the next batch starts with (1 = a quarter of the metamers, 4 = all) */
+    /* k-mer coverage (mtb_index_coverage_*): the hits of the classify call in work, per species + MTB_COV_EXTRA words, committed into the index's bins at
+     * its successful end (CovCall).  Outside the buffer table: an out-of-memory retry inside the call releases the workspace.  Lanes borrow the parent's. */
+    unsigned long long *d_cov_pend = nullptr; uint64_t cov_pend_words = 0; bool cov_call = false;
     MtbOptions opt;                                  /* the experiment / diagnosis switches: the MTB_* environment at mtb_ctx_create, mtb_ctx_set_option afterwards (mtb_options.h) */
 };
 template <typename T> static T *scal(mtb_ctx *c, Scal s) { return (T *)(c->d_scal + s); }
@@ -246,6 +250,9 @@ struct mtb_index {
     mtb_index *parent = nullptr;     /* of a view */
     uint64_t open_chunks = 0, open_chunk_words = 0, open_peak_bytes = 0, open_free0 = 0;      /* mtb_index_open_stats */
     void *ipc_stage[4] = {nullptr, nullptr, nullptr, nullptr};       /* mtb_index_export: copies of the arrays too small for an inter-process handle of their own */
+    bool is_part = false;            /* opened by mtb_index_open_part */
+    /* k-mer coverage (mtb_index_coverage_begin .. _end): one bit per entry position; hits per species + MTB_COV_EXTRA words */
+    uint32_t *d_cov_bits = nullptr; unsigned long long *d_cov_hits = nullptr;
 };
 
 enum ResKind { RES_ROWS = 0, RES_TAX = 1, RES_CNT = 2 };    /* the two device-side result sets of the asynchronous path: rows, packed taxID:count lists */
@@ -444,6 +451,7 @@ void mtb_ctx_destroy(mtb_ctx *c) {
     if (c->d_tabs && !c->is_lane) e = hipFree(c->d_tabs);
     if (c->d_scal) e = hipFree(c->d_scal);
     if (c->d_ovfctr) e = hipFree(c->d_ovfctr);
+    if (c->d_cov_pend && !c->is_lane) e = hipFree(c->d_cov_pend);
     if (c->is_lane && c->stream) e = hipStreamDestroy(c->stream);
     if (c->down_stream) { e = hipStreamSynchronize(c->down_stream); e = hipStreamDestroy(c->down_stream); }
     if (c->down_ready) e = hipEventDestroy(c->down_ready);
@@ -771,6 +779,12 @@ struct IndexUse {
         if (own->packed != target) { mtb_status st = target ? ensure_packed_locked(own) : ensure_flat_locked(own); if (st != MTB_OK) return st; }
         own->users++; o = own;
         return MTB_OK;
+    }
+    /* the state as it is, unconverted (coverage): *packed says which */
+    void hold(mtb_index *ix, bool *packed) {
+        mtb_index *own = state_owner(ix);
+        std::unique_lock<std::mutex> lk(own->state_mu);
+        own->users++; o = own; *packed = own->packed;
     }
     void release() { if (!o) return; { std::lock_guard<std::mutex> lk(o->state_mu); o->users--; } o->state_cv.notify_all(); o = nullptr; }
     ~IndexUse() { release(); }
@@ -1647,7 +1661,9 @@ mtb_status mtb_index_open(mtb_ctx *c, const char *dbdir, const char *taxonomy_di
 }
 mtb_status mtb_index_open_part(mtb_ctx *c, const char *dbdir, const char *taxonomy_dir, mtb_params *params, uint32_t part, uint32_t n_parts,
                                mtb_index **out) {
-    return open_impl(c, dbdir, taxonomy_dir, params, part, n_parts, out);
+    STCHK(open_impl(c, dbdir, taxonomy_dir, params, part, n_parts, out));
+    (*out)->is_part = true;
+    return MTB_OK;
 }
 mtb_status mtb_index_part_bounds(const char *dbdir, uint32_t n_parts, uint64_t *bounds) {
     if (!dbdir || !bounds || n_parts == 0) return fail(MTB_ERR_ARG, "NULL argument");
@@ -1866,6 +1882,8 @@ void mtb_index_close(mtb_index *ix) {
     if (ix->d_under) e = hipFree(ix->d_under);
     if (ix->d_accleaf) e = hipFree(ix->d_accleaf);
     if (ix->d_node) e = hipFree(ix->d_node);
+    if (ix->d_cov_bits) e = hipFree(ix->d_cov_bits);
+    if (ix->d_cov_hits) e = hipFree(ix->d_cov_hits);
     (void)e;
     delete ix;
 }
@@ -2507,6 +2525,204 @@ static mtb_status download_packed(mtb_ctx *c, mtb_result *d_res, const int32_t *
     return MTB_OK;
 }
 
+/* ---- k-mer coverage (include/mtb.h: mtb_index_coverage_*; kernels_coverage.h; the rule: tests/coverage_spec.py) ---- */
+static uint64_t cov_bitmap_words(const mtb_index *ix) { return std::max<uint64_t>((ix->T + 31) / 32, 1); }
+static uint64_t cov_bin_words(const mtb_index *ix) { return (uint64_t)ix->tax.max_id + 1 + MTB_COV_EXTRA; }
+static dim3 cov_grid(uint64_t n, uint64_t per_block, uint64_t most) { return dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + per_block - 1) / per_block, most))); }
+/* The pending hits of one top-level classify call (or stage call): cleared at its start, moved into the index's bins at its successful end, left
+ * behind (and cleared by the next call) after a failure.  An entry point called by another one finds the call open and does nothing. */
+struct CovCall {
+    mtb_ctx *c = nullptr; mtb_index *ix = nullptr;
+    mtb_status begin(mtb_ctx *c_, mtb_index *ix_) {
+        if (!ix_->d_cov_bits || c_->cov_call) return MTB_OK;
+        const uint64_t words = cov_bin_words(ix_);
+        if (c_->cov_pend_words < words) {
+            if (c_->d_cov_pend) { hipError_t e = hipFree(c_->d_cov_pend); (void)e; c_->d_cov_pend = nullptr; c_->cov_pend_words = 0; }
+            if (hipMalloc((void **)&c_->d_cov_pend, words * 8) != hipSuccess) { c_->d_cov_pend = nullptr; (void)hipGetLastError(); return fail(MTB_ERR_OOM, "no HBM for the pending coverage bins"); }
+            c_->cov_pend_words = words;
+        }
+        HIPCHK(hipMemsetAsync(c_->d_cov_pend, 0, words * 8, c_->stream));
+        HIPCHK(hipStreamSynchronize(c_->stream));          /* the lanes add from streams of their own */
+        for (mtb_ctx *l : c_->lanes) { l->d_cov_pend = c_->d_cov_pend; l->cov_pend_words = c_->cov_pend_words; }
+        c = c_; ix = ix_; c->cov_call = true;
+        return MTB_OK;
+    }
+    mtb_status end(mtb_status st) {
+        if (!c) return st;
+        mtb_ctx *cc = c; c = nullptr; cc->cov_call = false;
+        if (st != MTB_OK) return st;
+        const uint64_t words = cov_bin_words(ix);
+        hipLaunchKernelGGL(k_cov_commit, cov_grid(words, 256, ~0u), dim3(256), 0, cc->stream, ix->d_cov_hits, cc->d_cov_pend, words, (uint64_t)ix->tax.max_id + 1 + MTB_COV_N_BATCHES, 1u);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(cc->stream));
+        return MTB_OK;
+    }
+    ~CovCall() { if (c) c->cov_call = false; }
+};
+/* rs[0, n_reads) from the rows, then the marks and pending hits of d_q[0, n) (seq 1-based into the rows), on the context's stream.  `use` holds the
+ * index in the state it is in; the caller releases it after the stream is synchronised. */
+static mtb_status dev_cov_mark(mtb_ctx *c, mtb_index *ix, const mtb_kmer *d_q, uint64_t n, const mtb_result *d_res, uint64_t n_reads, uint32_t *d_rs, IndexUse *use) {
+    if (!c->d_cov_pend || c->cov_pend_words < cov_bin_words(ix)) return fail(MTB_ERR_ARG, "k-mer coverage: no classify call is open on this context");
+    if (n_reads == 0 || n == 0) return MTB_OK;
+    hipStream_t st = c->stream;
+    hipLaunchKernelGGL(k_cov_read_species, cov_grid(n_reads, 256, ~0u), dim3(256), 0, st, d_res, n_reads, (const int32_t *)ix->d_tax2species, ix->tax.max_id, d_rs);
+    HIPCHK(hipGetLastError());
+    bool packed = false;
+    use->hold(ix, &packed);
+    const mtb_index_view v = index_view(ix); const mtb_dir_view dv = dir_view(ix);
+    const dim3 grid = cov_grid(n, 256, 1u << 14);
+    if (packed) hipLaunchKernelGGL((k_cov_mark<true, true>), grid, dim3(256), 0, st, d_q, n, (const uint32_t *)d_rs, n_reads, v, dv, ix->d_cov_bits, c->d_cov_pend);
+    else if (ix->d_dir) hipLaunchKernelGGL((k_cov_mark<false, true>), grid, dim3(256), 0, st, d_q, n, (const uint32_t *)d_rs, n_reads, v, dv, ix->d_cov_bits, c->d_cov_pend);
+    else hipLaunchKernelGGL((k_cov_mark<false, false>), grid, dim3(256), 0, st, d_q, n, (const uint32_t *)d_rs, n_reads, v, dv, ix->d_cov_bits, c->d_cov_pend);
+    HIPCHK(hipGetLastError());
+    return MTB_OK;
+}
+
+extern "C" {
+
+mtb_status mtb_index_coverage_begin(mtb_index *ix) {
+    if (!ix) return fail(MTB_ERR_ARG, "NULL index");
+    if (ix->parent || ix->is_part) return fail(MTB_ERR_UNSUPPORTED, "k-mer coverage needs a whole index: not a view (mtb_index_slice) or a part (mtb_index_open_part)");
+    if (ix->d_cov_bits) return fail(MTB_ERR_ARG, "k-mer coverage is already on for this index");
+    HIPCHK(hipSetDevice(ix->ctx->device));
+    uint32_t *bits = nullptr; unsigned long long *hits = nullptr;
+    const uint64_t words = cov_bitmap_words(ix), bins = cov_bin_words(ix);
+    struct Guard { uint32_t *&b; unsigned long long *&h; ~Guard() { hipError_t e = hipSuccess; if (b) e = hipFree(b); if (h) e = hipFree(h); (void)e; } } guard{bits, hits};
+    if (hipMalloc((void **)&bits, words * 4) != hipSuccess) { bits = nullptr; (void)hipGetLastError(); return fail(MTB_ERR_OOM, "no HBM for the coverage bitmap (" + std::to_string(words * 4) + " bytes)"); }
+    if (hipMalloc((void **)&hits, bins * 8) != hipSuccess) { hits = nullptr; (void)hipGetLastError(); return fail(MTB_ERR_OOM, "no HBM for the coverage bins"); }
+    HIPCHK(hipMemsetAsync(bits, 0, words * 4, ix->ctx->stream)); HIPCHK(hipMemsetAsync(hits, 0, bins * 8, ix->ctx->stream));
+    HIPCHK(hipStreamSynchronize(ix->ctx->stream));
+    ix->d_cov_bits = bits; ix->d_cov_hits = hits;
+    bits = nullptr; hits = nullptr;
+    return MTB_OK;
+}
+
+mtb_status mtb_index_coverage_end(mtb_index *ix) {
+    if (!ix) return fail(MTB_ERR_ARG, "NULL index");
+    if (!ix->d_cov_bits) return fail(MTB_ERR_ARG, "k-mer coverage is not on for this index");
+    HIPCHK(hipSetDevice(ix->ctx->device));
+    hipError_t e = hipFree(ix->d_cov_bits); e = hipFree(ix->d_cov_hits); (void)e;
+    ix->d_cov_bits = nullptr; ix->d_cov_hits = nullptr;
+    return MTB_OK;
+}
+
+mtb_status mtb_index_coverage_merge(mtb_index *dst, mtb_index *src) {
+    if (!dst || !src || dst == src) return fail(MTB_ERR_ARG, "two different indices are needed");
+    if (!dst->d_cov_bits || !src->d_cov_bits) return fail(MTB_ERR_ARG, "k-mer coverage is not on for both indices");
+    if (dst->T != src->T || dst->tax.max_id != src->tax.max_id) return fail(MTB_ERR_ARG, "the indices differ in size: only a clone and its source can be merged");
+    mtb_ctx *dc = dst->ctx, *sc = src->ctx;
+    HIPCHK(hipSetDevice(sc->device)); HIPCHK(hipStreamSynchronize(sc->stream));
+    HIPCHK(hipSetDevice(dc->device));
+    hipStream_t st = dc->stream;
+    const uint64_t words = cov_bitmap_words(dst), bins = cov_bin_words(dst);
+    const uint64_t stage_bytes = std::min<uint64_t>(64ull << 20, std::max<uint64_t>(std::max(words * 4, bins * 8), 256));      /* a multiple of 8 */
+    void *stage = nullptr;
+    if (hipMalloc(&stage, stage_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MTB_ERR_OOM, "no HBM for the merge's staging buffer"); }
+    struct Guard { void *p; ~Guard() { hipError_t e = hipFree(p); (void)e; } } guard{stage};
+    auto fetch = [&](const void *from, size_t bytes) -> mtb_status {
+        if (sc->device == dc->device) HIPCHK(hipMemcpyAsync(stage, from, bytes, hipMemcpyDeviceToDevice, st));
+        else HIPCHK(hipMemcpyPeerAsync(stage, dc->device, from, sc->device, bytes, st));
+        return MTB_OK;
+    };
+    for (uint64_t w = 0; w < words; w += stage_bytes / 4) {
+        const uint64_t m = std::min<uint64_t>(stage_bytes / 4, words - w);
+        STCHK(fetch(src->d_cov_bits + w, m * 4));
+        hipLaunchKernelGGL(k_cov_or, cov_grid(m, 256, 1u << 14), dim3(256), 0, st, dst->d_cov_bits + w, (const uint32_t *)stage, m);
+        HIPCHK(hipGetLastError());
+    }
+    for (uint64_t w = 0; w < bins; w += stage_bytes / 8) {
+        const uint64_t m = std::min<uint64_t>(stage_bytes / 8, bins - w);
+        STCHK(fetch(src->d_cov_hits + w, m * 8));
+        hipLaunchKernelGGL(k_cov_commit, cov_grid(m, 256, ~0u), dim3(256), 0, st, dst->d_cov_hits + w, (unsigned long long *)stage, m, ~0ull, 0u);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    return MTB_OK;
+}
+
+mtb_status mtb_index_coverage_report(mtb_index *ix, uint64_t *distinct, uint64_t *hits, uint64_t *total, uint64_t cap, mtb_coverage_stats *stats) {
+    if (!ix) return fail(MTB_ERR_ARG, "NULL index");
+    if (!ix->d_cov_bits) return fail(MTB_ERR_ARG, "k-mer coverage is not on for this index");
+    const uint64_t n_bins = (uint64_t)ix->tax.max_id + 1;
+    if ((distinct || hits || total) && cap < n_bins)
+        return fail(MTB_ERR_CAPACITY, "the arrays hold " + std::to_string(cap) + " entries, the taxonomy needs " + std::to_string(n_bins));
+    mtb_ctx *c = ix->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    /* u32 bins of one pass: total and distinct, one array per XCD each; their u64 sums; the popcount */
+    const uint64_t stride = (n_bins + 63) & ~63ull, pass_words = 2 * stride * MTB_AUDIT_REPLICAS;
+    char *mem = nullptr;
+    const size_t bytes = pass_words * 4 + 2 * n_bins * 8 + 8;
+    if (hipMalloc((void **)&mem, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MTB_ERR_OOM, "no HBM for the coverage report's bins"); }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    struct Guard { char *p; hipEvent_t &a, &b; ~Guard() { hipError_t e = hipFree(p); if (a) e = hipEventDestroy(a); if (b) e = hipEventDestroy(b); (void)e; } } guard{mem, e0, e1};
+    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
+    unsigned long long *d_sum = (unsigned long long *)mem, *d_pop = d_sum + 2 * n_bins;      /* [0, n_bins) total, [n_bins, 2 n_bins) distinct */
+    uint32_t *d_pass = (uint32_t *)(d_pop + 1);
+    HIPCHK(hipMemsetAsync(mem, 0, bytes, st));
+    HIPCHK(hipEventRecord(e0, st));
+    IndexUse use; bool packed = false;
+    use.hold(ix, &packed);
+    const mtb_index_view v = index_view(ix);
+    const uint64_t SEG = 1ull << 31;                 /* entries per pass: a u32 bin cannot overflow */
+    for (uint64_t t0 = 0; t0 < ix->T; t0 += SEG) {
+        const uint64_t m = std::min<uint64_t>(SEG, ix->T - t0);
+        const dim3 grid = cov_grid(m, 256ull * MTB_AUDIT_PER_LANE, 1u << 16);
+        if (packed) hipLaunchKernelGGL(k_cov_count<true>, grid, dim3(256), 0, st, v, t0, m, (const uint32_t *)ix->d_cov_bits, d_pass, d_pass + stride * MTB_AUDIT_REPLICAS, stride);
+        else hipLaunchKernelGGL(k_cov_count<false>, grid, dim3(256), 0, st, v, t0, m, (const uint32_t *)ix->d_cov_bits, d_pass, d_pass + stride * MTB_AUDIT_REPLICAS, stride);
+        HIPCHK(hipGetLastError());
+        for (int k = 0; k < 2; k++) {
+            uint32_t *bins = d_pass + (uint64_t)k * stride * MTB_AUDIT_REPLICAS;
+            hipLaunchKernelGGL(k_audit_bins_reduce, cov_grid(n_bins, 256, ~0u), dim3(256), 0, st, bins, n_bins, stride);
+            hipLaunchKernelGGL(k_cov_accumulate, cov_grid(n_bins, 256, ~0u), dim3(256), 0, st, d_sum + (uint64_t)k * n_bins, bins, n_bins);
+            HIPCHK(hipGetLastError());
+            if (t0 + SEG < ix->T) HIPCHK(hipMemsetAsync(bins, 0, stride * MTB_AUDIT_REPLICAS * 4, st));       /* the other replicas, for the next pass */
+        }
+    }
+    hipLaunchKernelGGL(k_popcount_words, cov_grid(cov_bitmap_words(ix), 256, 4096), dim3(256), 0, st, (const uint32_t *)ix->d_cov_bits, cov_bitmap_words(ix), d_pop);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e1, st));
+    HIPCHK(hipEventSynchronize(e1));
+    use.release();
+    std::vector<unsigned long long> h_hits(cov_bin_words(ix));
+    unsigned long long n_marked = 0;
+    if (total) STCHK(d2h(c, total, d_sum, n_bins * 8));
+    if (distinct) STCHK(d2h(c, distinct, d_sum + n_bins, n_bins * 8));
+    STCHK(d2h(c, h_hits.data(), ix->d_cov_hits, h_hits.size() * 8));
+    STCHK(d2h(c, &n_marked, d_pop, 8));
+    if (hits) for (uint64_t s = 0; s < n_bins; s++) hits[s] = h_hits[s];
+    if (stats) {
+        memset(stats, 0, sizeof(*stats));
+        stats->n_targets = ix->T; stats->n_marked = n_marked;
+        for (uint64_t s = 0; s < n_bins; s++) stats->n_hits += h_hits[s];
+        stats->n_queries = h_hits[n_bins + MTB_COV_N_QUERIES]; stats->n_queries_counted = h_hits[n_bins + MTB_COV_N_COUNTED]; stats->n_batches = h_hits[n_bins + MTB_COV_N_BATCHES];
+        HIPCHK(hipEventElapsedTime(&stats->ms_count, e0, e1));
+    }
+    return MTB_OK;
+}
+
+mtb_status mtb_index_coverage_mark(mtb_ctx *c, mtb_index *ix, const mtb_kmer *kmers, uint64_t n, const mtb_result *results, uint64_t n_reads) {
+    if (!c || !ix || (n && !kmers) || (n_reads && !results)) return fail(MTB_ERR_ARG, "NULL argument");
+    if (!ix->d_cov_bits) return fail(MTB_ERR_ARG, "k-mer coverage is not on for this index");
+    for (uint64_t i = 0; i < n; i++)
+        if ((uint64_t)mtb_q_seq(kmers[i].qinfo) > n_reads)
+            return fail(MTB_ERR_ARG, "metamer " + std::to_string(i) + " names read " + std::to_string(mtb_q_seq(kmers[i].qinfo)) + " of " + std::to_string(n_reads));
+    HIPCHK(hipSetDevice(c->device));
+    if (n == 0 || n_reads == 0) return MTB_OK;
+    CovCall cov;
+    STCHK(cov.begin(c, ix));
+    mtb_kmer *d_q; mtb_result *d_r; uint32_t *d_rs;
+    STCHK(ensure(c, "kmersA", n, &d_q)); STCHK(ensure(c, "covrows", n_reads, &d_r)); STCHK(ensure(c, "covrs", n_reads, &d_rs));       /* (rows of their own: an asynchronous download may still read the result sets) */
+    STCHK(h2d(c, d_q, kmers, n * sizeof(mtb_kmer))); STCHK(h2d(c, d_r, results, n_reads * sizeof(mtb_result)));
+    IndexUse use;
+    mtb_status st = dev_cov_mark(c, ix, d_q, n, d_r, n_reads, d_rs, &use);
+    if (st == MTB_OK) { hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) st = fail(MTB_ERR_DEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(e)); }
+    use.release();
+    return cov.end(st);
+}
+
+} // extern "C"
+
 /* the sorted query metamers of a read range, and what the extractor said about them */
 struct SortedQueries {
     const mtb_kmer *d_s = nullptr; uint64_t nk = 0; int low_bits = 32;       /* low_bits: the bits the list is NOT sorted on (the join's tile windows follow the sort key) */
@@ -2624,6 +2840,8 @@ static mtb_status classify_attempt(mtb_ctx *c, mtb_index *ix, const mtb_params *
     if (n_reads == 0) return MTB_OK;
     hipStream_t st = c->stream; int32_t *d_ql, *d_ql2;
     STCHK(ensure(c, "qlen", n_reads, &d_ql)); STCHK(ensure(c, "qlen2", n_reads, &d_ql2));
+    uint32_t *d_cov_rs = nullptr;                    /* k-mer coverage on: the reads' species, for the marking behind the scoring */
+    if (ix->d_cov_bits) STCHK(ensure(c, "covrs", n_reads, &d_cov_rs));
     HIPCHK(hipEventRecord(c->ev[0], st));
     /* short reads: per-read slot segments, the query's ordinal (tagged into qinfo by the extractor) is the slot of its
      * first match.  Needs positions < 2^12 (16-byte slot records) and a moderate number of metamers per read; otherwise
@@ -2710,8 +2928,13 @@ static mtb_status classify_attempt(mtb_ctx *c, mtb_index *ix, const mtb_params *
         HIPCHK(hipEventRecord(c->ev[3], st));
         STCHK(score_join_order(c, ix, p, ml.d_out, nm, n_reads, d_rc, lens, out, n_taxcnt));
     }
+    /* k-mer coverage: the range is scored, so every metamer of it is counted once; the sorted list is still whole on all three branches (the
+     * scorers' scratch() is carved from the buffers that do NOT hold it, the long-read paths write buffers of their own) */
+    IndexUse cov_use;
+    if (d_cov_rs) STCHK(dev_cov_mark(c, ix, d_s, ex.nk, out.d_res, n_reads, d_cov_rs, &cov_use));
     HIPCHK(hipEventRecord(c->ev[6], st));
     HIPCHK(hipEventSynchronize(c->ev[6]));
+    cov_use.release();
     mtb_batch_stats &S = c->stats;
     float *const stage_ms[6] = {&S.ms_extract, &S.ms_sort, &S.ms_join, &S.ms_regroup, &S.ms_segsort, &S.ms_score};
     for (int k = 0; k < 6; k++) HIPCHK(hipEventElapsedTime(stage_ms[k], c->ev[k], c->ev[k + 1]));
@@ -2826,11 +3049,10 @@ static mtb_status classify_budgeted(mtb_ctx *c, mtb_index *ix, const mtb_params 
 
 extern "C" {
 
-mtb_status mtb_classify_batch_device(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const char *d_bases, const uint64_t *d_offs,
-                                     const char *d_bases2, const uint64_t *d_offs2, uint64_t n_reads, uint64_t n_bases_total,
-                                     mtb_result *d_results, int32_t *d_taxcnt_tax, uint32_t *d_taxcnt_cnt, uint64_t taxcnt_cap,
-                                     uint64_t *n_taxcnt) {
-    if (!c || !ix || !p || !n_taxcnt) return fail(MTB_ERR_ARG, "NULL argument");
+static mtb_status classify_batch_device_impl(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const char *d_bases, const uint64_t *d_offs,
+                                             const char *d_bases2, const uint64_t *d_offs2, uint64_t n_reads, uint64_t n_bases_total,
+                                             mtb_result *d_results, int32_t *d_taxcnt_tax, uint32_t *d_taxcnt_cnt, uint64_t taxcnt_cap,
+                                             uint64_t *n_taxcnt) {
     const size_t L = c->lanes.size();
     if (L < 2 || n_reads < 4096 * L)
         return classify_budgeted(c, ix, p, Reads{d_bases, d_offs, d_bases2, d_offs2, n_reads}, n_bases_total, ResultSink{d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, /* tc_base */ 0}, n_taxcnt);
@@ -2877,6 +3099,17 @@ mtb_status mtb_classify_batch_device(mtb_ctx *c, mtb_index *ix, const mtb_params
     return MTB_OK;
 }
 
+/* (k-mer coverage: every public classify entry point brackets its work with a CovCall; the outermost one commits the hits) */
+mtb_status mtb_classify_batch_device(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const char *d_bases, const uint64_t *d_offs,
+                                     const char *d_bases2, const uint64_t *d_offs2, uint64_t n_reads, uint64_t n_bases_total,
+                                     mtb_result *d_results, int32_t *d_taxcnt_tax, uint32_t *d_taxcnt_cnt, uint64_t taxcnt_cap,
+                                     uint64_t *n_taxcnt) {
+    if (!c || !ix || !p || !n_taxcnt) return fail(MTB_ERR_ARG, "NULL argument");
+    CovCall cov;
+    STCHK(cov.begin(c, ix));
+    return cov.end(classify_batch_device_impl(c, ix, p, d_bases, d_offs, d_bases2, d_offs2, n_reads, n_bases_total, d_results, d_taxcnt_tax, d_taxcnt_cnt, taxcnt_cap, n_taxcnt));
+}
+
 /* Device-side taxcnt slots of a batch: one per position bucket of every read (k_taxcnt_bound), sum floor((len + 3) / shift) + 2 <=
  * (bases + 3 reads) / shift + 2 reads.  The host arrays of the single-stream calls only receive the packed lists (download_packed), so their
  * capacity may be far smaller (2-3 entries per read is typical); MTB_ERR_CAPACITY reports what the lists need. */
@@ -2885,10 +3118,9 @@ static uint64_t taxcnt_device_slots(const mtb_params *p, uint64_t n_reads, uint6
     return (n_bases + 3 * n_reads) / (uint64_t)std::max(1, sp.dna_shift) + 2 * n_reads + 64;
 }
 
-mtb_status mtb_classify_batch(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const char *bases, const uint64_t *offs, const char *bases2,
-                              const uint64_t *offs2, uint64_t n_reads, mtb_result *results, int32_t *taxcnt_tax, uint32_t *taxcnt_cnt,
-                              uint64_t taxcnt_cap, uint64_t *n_taxcnt) {
-    if (!c || !ix || !p || !n_taxcnt) return fail(MTB_ERR_ARG, "NULL argument");
+static mtb_status classify_batch_impl(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const char *bases, const uint64_t *offs, const char *bases2,
+                                      const uint64_t *offs2, uint64_t n_reads, mtb_result *results, int32_t *taxcnt_tax, uint32_t *taxcnt_cnt,
+                                      uint64_t taxcnt_cap, uint64_t *n_taxcnt) {
     HIPCHK(hipSetDevice(c->device));
     *n_taxcnt = 0;
     if (n_reads == 0) return MTB_OK;
@@ -2904,6 +3136,15 @@ mtb_status mtb_classify_batch(mtb_ctx *c, mtb_index *ix, const mtb_params *p, co
     STCHK(d2h(c, results, d_res, n_reads * sizeof(mtb_result)));
     if (*n_taxcnt) { STCHK(d2h(c, taxcnt_tax, d_tt, *n_taxcnt * 4)); STCHK(d2h(c, taxcnt_cnt, d_tc, *n_taxcnt * 4)); }
     return MTB_OK;
+}
+
+mtb_status mtb_classify_batch(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const char *bases, const uint64_t *offs, const char *bases2,
+                              const uint64_t *offs2, uint64_t n_reads, mtb_result *results, int32_t *taxcnt_tax, uint32_t *taxcnt_cnt,
+                              uint64_t taxcnt_cap, uint64_t *n_taxcnt) {
+    if (!c || !ix || !p || !n_taxcnt) return fail(MTB_ERR_ARG, "NULL argument");
+    CovCall cov;
+    STCHK(cov.begin(c, ix));
+    return cov.end(classify_batch_impl(c, ix, p, bases, offs, bases2, offs2, n_reads, results, taxcnt_tax, taxcnt_cnt, taxcnt_cap, n_taxcnt));
 }
 
 /* Host ingest at device rate: pinned host memory for the batch buffers, and the bases as 2-bit codes. */
@@ -3034,7 +3275,10 @@ extern "C" {
 mtb_status mtb_classify_batch_packed(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const uint8_t *packed2, const uint8_t *nmask, const uint32_t *lens,
                                      const uint8_t *packed2_mate, const uint8_t *nmask_mate, const uint32_t *lens_mate, uint64_t n_reads,
                                      mtb_result *results, int32_t *taxcnt_tax, uint32_t *taxcnt_cnt, uint64_t taxcnt_cap, uint64_t *n_taxcnt) {
-    return classify_packed_impl(c, ix, p, packed2, nmask, lens, packed2_mate, nmask_mate, lens_mate, n_reads, results, taxcnt_tax, taxcnt_cnt, taxcnt_cap, n_taxcnt, false);
+    if (!c || !ix || !p || !n_taxcnt) return fail(MTB_ERR_ARG, "NULL argument");
+    CovCall cov;
+    STCHK(cov.begin(c, ix));
+    return cov.end(classify_packed_impl(c, ix, p, packed2, nmask, lens, packed2_mate, nmask_mate, lens_mate, n_reads, results, taxcnt_tax, taxcnt_cnt, taxcnt_cap, n_taxcnt, false));
 }
 
 /* The same with the results on their way back while the next batch computes: returns once the copies of the rows and of the packed
@@ -3046,7 +3290,10 @@ mtb_status mtb_classify_batch_packed(mtb_ctx *c, mtb_index *ix, const mtb_params
 mtb_status mtb_classify_batch_packed_async(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const uint8_t *packed2, const uint8_t *nmask, const uint32_t *lens,
                                            const uint8_t *packed2_mate, const uint8_t *nmask_mate, const uint32_t *lens_mate, uint64_t n_reads,
                                            mtb_result *results, int32_t *taxcnt_tax, uint32_t *taxcnt_cnt, uint64_t taxcnt_cap, uint64_t *n_taxcnt) {
-    mtb_status st = classify_packed_impl(c, ix, p, packed2, nmask, lens, packed2_mate, nmask_mate, lens_mate, n_reads, results, taxcnt_tax, taxcnt_cnt, taxcnt_cap, n_taxcnt, true);
+    if (!c || !ix || !p || !n_taxcnt) return fail(MTB_ERR_ARG, "NULL argument");
+    CovCall cov;
+    STCHK(cov.begin(c, ix));
+    mtb_status st = cov.end(classify_packed_impl(c, ix, p, packed2, nmask, lens, packed2_mate, nmask_mate, lens_mate, n_reads, results, taxcnt_tax, taxcnt_cnt, taxcnt_cap, n_taxcnt, true));
     if (st != MTB_OK && c && c->down_pending) {     /* the contract holds on every path: the previous call's copies are complete when this one returns */
         hipError_t e = hipEventSynchronize(c->down_done); (void)e; c->down_pending = false;
     }
