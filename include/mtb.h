@@ -704,6 +704,58 @@ mtb_status mtb_index_coverage_merge(mtb_index *dst, mtb_index *src);
 mtb_status mtb_index_coverage_report(mtb_index *, uint64_t *distinct, uint64_t *hits, uint64_t *total, uint64_t cap, mtb_coverage_stats *);
 mtb_status mtb_index_coverage_mark(mtb_ctx *, mtb_index *, const mtb_kmer *kmers, uint64_t n, const mtb_result *results, uint64_t n_reads);
 
+/* ---- inspection of a database directory: LCA k-mer counts per taxon ----------------------------------------------------------
+ * kraken2-inspect's question, and the reference's expert command count-common-kmers (src/util/count_common_kmers.cpp:43-105): for
+ * every distinct k-mer, at which node of the taxonomy do its owners meet, and how many k-mers does each node hold that way.  The
+ * rule is stated once, in tests/inspect_spec.py; in short: a GROUP is a maximal run of consecutive entries (file order) with equal
+ * keys -- level 0 ("dna"): the 64-bit value; level 1 ("aa"): value >> 24, the run of candidates the join walks for one amino-acid
+ * part --, t(g) is the LCA of its members' ids that the taxonomy knows (a canonical node), and
+ *     distinct[t(g)] += 1     entries[t(g)] += |g|  (all members)
+ * A group without a known id adds to n_orphan_groups / n_orphan_entries and to no bin.  size_hist[k] counts the groups with
+ * floor(log2 |g|) == k; first_max_group is the entry index of the first member of the first largest group (UINT64_MAX: no entry).
+ * Departures from the reference: ids are info & info_mask as everywhere here (it masks bit 31 unconditionally); the database's last
+ * entry is part of its group (its loop leaves it out); an orphan group is counted (it would dereference null).
+ * Nothing is sorted or validated: on an unsound database the numbers are defined and meaningless -- mtb_database_audit
+ * (--validate-db) says whether a database is sound.
+ * One streaming pass, as the audit's: the index is never resident; peak device memory is one chunk, the taxonomy, 32 B per 1024
+ * entries of a chunk and the bins (2 x 8 x 4 B + 2 x 8 B per taxonomy id).  The same file checks, wording and MTB_ERR_IO before any
+ * device work; Reduced_alphabet 1: MTB_ERR_UNSUPPORTED; a level other than 0 or 1: MTB_ERR_ARG.  distinct / entries (host; each may
+ * be NULL; cap entries each, at least mtb_tax_max_id + 1): else MTB_ERR_CAPACITY, the message gives the entries needed, out->n_taxa
+ * holds them too, nothing else is written.
+ * Times: host-clock ms of the file reads, device ms of decode / of the inspection (events: both kernels and the per-chunk sums of
+ * the bins), ms_bins = clearing and downloading the bins, ms_total = the call. */
+#define MTB_INSPECT_HIST_SLOTS 40
+typedef struct {
+    uint64_t n_entries, n_groups, max_group, first_max_group;
+    uint64_t n_orphan_groups, n_orphan_entries;
+    uint64_t size_hist[MTB_INSPECT_HIST_SLOTS];
+    uint64_t n_taxa;                                   /* mtb_tax_max_id + 1: the entries distinct / entries need */
+    uint64_t n_chunks;                                 /* device passes */
+    float    ms_read, ms_decode, ms_inspect, ms_bins, ms_total;
+} mtb_inspect_report;
+mtb_status mtb_database_inspect(mtb_ctx *, const char *dbdir, const char *taxonomy_dir /* as mtb_index_open */,
+                                mtb_params *params /* in/out, as mtb_index_open */, uint64_t chunk_words /* 0: as mtb_database_audit */,
+                                int level /* 0: dna, 1: aa */, uint64_t *distinct, uint64_t *entries /* host, may be NULL */,
+                                uint64_t cap /* entries; need mtb_tax_max_id + 1 */, mtb_inspect_report *out);
+/* stage call (parity seam), host arrays: entries 0..n-1 as values[] / info[], through exactly the device code of the directory call,
+ * entries_per_pass of them per device pass (0: all in one; else rounded up to a multiple of 4).  The taxonomy is an open index's
+ * (ix; on this context's device) or, with ix NULL, the dump files of taxonomy_dir.  kernels' tile: mtb_inspect_tile_entries(). */
+mtb_status mtb_inspect_records(mtb_ctx *, const mtb_index *ix /* or NULL */, const char *taxonomy_dir /* read iff ix is NULL */,
+                               const uint64_t *values, const uint32_t *info, uint64_t n, uint32_t info_mask, int level,
+                               uint64_t entries_per_pass, uint64_t *distinct, uint64_t *entries, uint64_t cap, mtb_inspect_report *out);
+uint32_t   mtb_inspect_tile_entries(void);
+/* The report of one level.  tsv_path (may be NULL): a header line, then one row per canonical node with a non-zero clade sum,
+ * ascending internal id: original_taxid, rank, name, distinct, entries, distinct_clade, entries_clade (a clade sum is the node's own
+ * bin plus its descendants'; u64 throughout -- the classify report's 32-bit counts are not used).  summary (may be NULL; summary_cap
+ * bytes, else MTB_ERR_CAPACITY): the by-rank summary in count-common-kmers' wording, ranks in its order (:107-109), taxon 1 as
+ * `root`, then -- a departure: it drops them silently -- every other rank with a count, alphabetically.
+ * The taxonomy: ix's; with ix NULL the one mtb_database_inspect loads for dbdir / taxonomy_dir; with dbdir NULL too the dump files of
+ * taxonomy_dir.  n: entries of distinct / entries, at least mtb_tax_max_id + 1.  DBDIR/kmer_lca_report.tsv (level 0) and
+ * DBDIR/kmer_lca_report_aa.tsv (level 1) are where mtb_build --inspect writes. */
+mtb_status mtb_inspect_write_report(const mtb_index *ix, const char *dbdir, const char *taxonomy_dir, const uint64_t *distinct,
+                                    const uint64_t *entries, uint64_t n, uint64_t n_groups, const char *tsv_path,
+                                    char *summary, uint64_t summary_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,5 +229,15 @@ inline mtb_audit_report auditDatabase(mtb_ctx *ctx, const std::string &dbDir, co
     return r;
 }
 
+/* count-common-kmers (src/util/count_common_kmers.cpp): LCA k-mer counts per taxon in one streaming pass: mtb_database_inspect, passed
+ * through.  level 0: groups of equal values, 1: of equal amino-acid parts.  distinct / entries: cap entries each (mtb_tax_max_id + 1
+ * are needed; too few throw with that number in the message), or both NULL for the report alone. */
+inline mtb_inspect_report inspectDatabase(mtb_ctx *ctx, const std::string &dbDir, const std::string &taxonomyDir, LocalParameters par, int level,
+                                          uint64_t *distinct, uint64_t *entries, uint64_t cap, uint64_t chunkWords = 0) {
+    mtb_inspect_report r;
+    check(mtb_database_inspect(ctx, dbDir.c_str(), taxonomyDir.empty() ? nullptr : taxonomyDir.c_str(), &par, chunkWords, level, distinct, entries, cap, &r));
+    return r;
+}
+
 } // namespace mtb
 #endif

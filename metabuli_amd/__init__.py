@@ -284,6 +284,43 @@ class Context:
         rep = {name: (float(getattr(r, name)) if name.startswith("ms_") else int(getattr(r, name))) for name, _ in AuditReport._fields_}
         return rep, arr
 
+    def _inspect(self, call, want_bins):
+        """the capacity probe and the call of mtb_database_inspect / mtb_inspect_records -> (report dict, distinct, entries)"""
+        r = InspectReport()
+        distinct = entries = None
+        if want_bins:
+            # the arrays' size is the taxonomy's largest id + 1: arrays without room are refused with that number, before any device work
+            one = np.zeros(1, np.uint64)
+            st = call(_p(one), _p(one), C.c_uint64(0), C.byref(r))
+            if st != MTB_ERR_CAPACITY:
+                _chk(st)
+            distinct = np.zeros(int(r.n_taxa), np.uint64); entries = np.zeros(int(r.n_taxa), np.uint64)
+        _chk(call(_p(distinct), _p(entries), C.c_uint64(len(distinct) if want_bins else 0), C.byref(r)))
+        rep = {name: (float(getattr(r, name)) if name.startswith("ms_") else int(getattr(r, name))) for name, _ in InspectReport._fields_ if name != "size_hist"}
+        rep["size_hist"] = [int(x) for x in r.size_hist]
+        return rep, distinct, entries
+
+    def inspect_database(self, dbdir, taxonomy_dir=None, level="dna", chunk_words=0, params=None, bins=True):
+        """mtb_database_inspect: one streaming pass over a database directory of any size -> (the report as a dict, distinct, entries):
+        for every group of entries with equal keys (level "dna": the value, "aa": its amino-acid part) the LCA of its members;
+        distinct[t] = groups that meet at node t, entries[t] = their members (uint64 arrays indexed by taxon id, None without `bins`)"""
+        params = params if params is not None else default_params()
+        lv = C.c_int(INSPECT_LEVELS[level] if isinstance(level, str) else int(level))
+        head = (self.h, dbdir.encode(), taxonomy_dir.encode() if taxonomy_dir else None, C.byref(params), C.c_uint64(int(chunk_words)), lv)
+        return self._inspect(lambda *tail: self.L.mtb_database_inspect(*head, *tail), bins)
+
+    def inspect_records(self, values, info, index=None, taxonomy_dir=None, level="dna", info_mask=0xFFFFFFFF, entries_per_pass=0, bins=True):
+        """mtb_inspect_records (stage call of the inspection's kernels): the entries values[] / info[] in file order through the device
+        code of inspect_database, entries_per_pass of them per device pass (0: one pass); the taxonomy is `index`'s or the dump
+        files of `taxonomy_dir`"""
+        v = np.ascontiguousarray(values, dtype=np.uint64); i = np.ascontiguousarray(info, dtype=np.uint32)
+        if len(v) != len(i):
+            raise ValueError("values and info differ in length")
+        lv = C.c_int(INSPECT_LEVELS[level] if isinstance(level, str) else int(level))
+        head = (self.h, index.h if index is not None else None, taxonomy_dir.encode() if taxonomy_dir else None, _p(v), _p(i), C.c_uint64(len(v)),
+                C.c_uint32(int(info_mask)), lv, C.c_uint64(int(entries_per_pass)))
+        return self._inspect(lambda *tail: self.L.mtb_inspect_records(*head, *tail), bins)
+
     def merge_sorted(self, a, b):
         """mtb_merge_sorted (stage call of the merge kernels): two kmer_dt lists, each ascending in (value, qinfo) -> their merge"""
         a = np.ascontiguousarray(a, dtype=kmer_dt); b = np.ascontiguousarray(b, dtype=kmer_dt)
@@ -594,6 +631,35 @@ class AuditReport(C.Structure):
                                           "n_group_disorder", "first_group_disorder", "n_unknown_ids", "first_unknown_id", "n_unlisted_ids", "first_unlisted_id",
                                           "n_no_species", "n_checkpoints", "n_bad_checkpoints", "first_bad_checkpoint", "n_species", "n_chunks")] + \
                [("valid", C.c_int32), ("canonical", C.c_int32)] + [(n, C.c_float) for n in ("ms_read", "ms_decode", "ms_check", "ms_hist", "ms_total")]
+
+
+class InspectReport(C.Structure):
+    """mtb_inspect_report (include/mtb.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_entries", "n_groups", "max_group", "first_max_group", "n_orphan_groups", "n_orphan_entries")] + \
+               [("size_hist", C.c_uint64 * 40), ("n_taxa", C.c_uint64), ("n_chunks", C.c_uint64)] + \
+               [(n, C.c_float) for n in ("ms_read", "ms_decode", "ms_inspect", "ms_bins", "ms_total")]
+
+
+INSPECT_LEVELS = {"dna": 0, "aa": 1}
+INSPECT_REPORT_FILES = {0: "kmer_lca_report.tsv", 1: "kmer_lca_report_aa.tsv"}      # where mtb_build --inspect writes, in DBDIR
+
+
+def inspect_tile_entries():
+    """entries per tile of the inspection's kernels (MTB_INSPECT_TILE, kernels_inspect.h)"""
+    L = lib()
+    L.mtb_inspect_tile_entries.restype = C.c_uint32
+    return int(L.mtb_inspect_tile_entries())
+
+
+def write_inspect_report(distinct, entries, n_groups, tsv_path=None, index=None, dbdir=None, taxonomy_dir=None):
+    """mtb_inspect_write_report: the TSV of one level (tsv_path, may be None) -> the by-rank summary as text.  The taxonomy is
+    `index`'s, else the database directory's (with taxonomy_dir as for open_index), else the dump files of taxonomy_dir."""
+    d = np.ascontiguousarray(distinct, dtype=np.uint64); e = np.ascontiguousarray(entries, dtype=np.uint64)
+    buf = C.create_string_buffer(1 << 16)
+    _chk(lib().mtb_inspect_write_report(index.h if index is not None else None, dbdir.encode() if dbdir else None, taxonomy_dir.encode() if taxonomy_dir else None,
+                                        _p(d), _p(e), C.c_uint64(min(len(d), len(e))), C.c_uint64(int(n_groups)), tsv_path.encode() if tsv_path else None,
+                                        buf, C.c_uint64(len(buf))))
+    return buf.value.decode()
 
 
 def write_species_counts(dbdir, counts):

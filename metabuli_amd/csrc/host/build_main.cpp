@@ -24,6 +24,9 @@
  *   mtb_build --audit 1 - - TAXONOMYDIR DBDIR      audit only (mtb_database_audit): the report is printed, DBDIR/sp2uniqKmerCnt (the
  *             reference's per-species entry counts, Classifier.cpp:390-440) is written, exit 1 if the database is not valid
  *   --validate-db 1 on any build, update or merge: OUTDB is audited after it is written; the run fails if it is not canonical
+ *   mtb_build --inspect 1 [--inspect-level dna|aa|both] - - TAXONOMYDIR DBDIR      inspect only (mtb_database_inspect): LCA k-mer counts per
+ *   taxon in DBDIR/kmer_lca_report.tsv (dna) / kmer_lca_report_aa.tsv (aa), count-common-kmers' by-rank summary on stdout; with --audit 1
+ *   both in one run.  --inspect 1 on any build, update or merge: OUTDB is inspected after it is written
  *
  *   mtb_build --add-db DB [--add-db DB2]... [--select-taxid A,B,..] [--exclude-taxid C,..] - - TAXONOMYDIR OUTDB
  *             a subset of a database, or a merge without a clade (mtb_merge_databases_filtered; the flag names and the comma syntax
@@ -107,10 +110,40 @@ static mtb_audit_report audit(mtb_ctx *ctx, const std::string &db, const std::st
     return r;
 }
 
+/* mtb_database_inspect of `db` at the chosen levels (bit 0: dna, bit 1: aa): DBDIR/kmer_lca_report.tsv / kmer_lca_report_aa.tsv, the
+ * by-rank summary in count-common-kmers' wording and one line with the groups, the largest one and the size histogram */
+static void inspect(mtb_ctx *ctx, const std::string &db, const std::string &taxdir, const mtb_params &par0, int levels) {
+    for (int level = 0; level < 2; level++) {
+        if (!(levels & (1 << level))) continue;
+        printf("Counting common k-mers by taxonomic rank: %s (%s level)\n", db.c_str(), level ? "aa" : "dna");
+        mtb_params par = par0;
+        mtb_inspect_report r;
+        uint64_t none = 0;       /* the arrays' size is the taxonomy's: arrays without room are refused with that number before any device work */
+        const mtb_status q = mtb_database_inspect(ctx, db.c_str(), taxdir.c_str(), &par, 0, level, &none, &none, 0, &r);
+        if (q != MTB_ERR_CAPACITY) chk(q, ("inspect " + db).c_str());
+        std::vector<uint64_t> distinct((size_t)r.n_taxa, 0), entries((size_t)r.n_taxa, 0);
+        chk(mtb_database_inspect(ctx, db.c_str(), taxdir.c_str(), &par, 0, level, distinct.data(), entries.data(), distinct.size(), &r), ("inspect " + db).c_str());
+        const std::string tsv = db + (level ? "/kmer_lca_report_aa.tsv" : "/kmer_lca_report.tsv");
+        std::vector<char> summary(1 << 16);
+        chk(mtb_inspect_write_report(nullptr, db.c_str(), taxdir.c_str(), distinct.data(), entries.data(), distinct.size(), r.n_groups, tsv.c_str(), summary.data(), summary.size()),
+            "write the inspection report");
+        fputs(summary.data(), stdout);
+        printf("Inspected (%s): %llu entries in %llu chunks, %llu groups (%llu groups, %llu entries in all, without a known id), largest group %llu at entry %lld; groups by floor(log2 size):",
+               level ? "aa" : "dna", (unsigned long long)r.n_entries, (unsigned long long)r.n_chunks, (unsigned long long)r.n_groups, (unsigned long long)r.n_orphan_groups,
+               (unsigned long long)r.n_orphan_entries, (unsigned long long)r.max_group, r.max_group ? (long long)r.first_max_group : -1ll);
+        int top = 0;
+        for (int k = 0; k < MTB_INSPECT_HIST_SLOTS; k++) if (r.size_hist[k]) top = k;
+        for (int k = 0; k <= top; k++) printf(" %llu", (unsigned long long)r.size_hist[k]);
+        printf("; read %.1f ms, decode %.1f ms, inspect %.1f ms, bins %.1f ms, total %.1f ms; report in %s\n", r.ms_read, r.ms_decode, r.ms_inspect, r.ms_bins, r.ms_total, tsv.c_str());
+    }
+    fflush(stdout);
+}
+
 int main(int argc, char **argv) {
     try {
         std::vector<std::string> add_db, pos;
         bool audit_only = false, validate_db = false;
+        bool inspect_on = false; int inspect_level_bits = 1;       /* --inspect 1; --inspect-level: bit 0 dna (default), bit 1 aa */
         std::string cds_list;
         std::vector<int32_t> select_ids, exclude_ids;
         bool filter_given = false;
@@ -144,6 +177,12 @@ int main(int argc, char **argv) {
             else if (a == "--device") device = atoi(val().c_str());
             else if (a == "--audit") audit_only = atoi(val().c_str()) != 0;
             else if (a == "--validate-db") validate_db = atoi(val().c_str()) != 0;
+            else if (a == "--inspect") { const std::string v = val(); if (v != "0" && v != "1") die("--inspect: '" + v + "' is not 0 or 1"); inspect_on = v == "1"; }
+            else if (a == "--inspect-level") {
+                const std::string v = val();
+                if (v == "dna") inspect_level_bits = 1; else if (v == "aa") inspect_level_bits = 2; else if (v == "both") inspect_level_bits = 3;
+                else die("--inspect-level: '" + v + "' is not dna, aa or both");
+            }
             else if (a == "--select-taxid") id_list(a, val(), &select_ids);
             else if (a == "--exclude-taxid") id_list(a, val(), &exclude_ids);
             else if (a.size() > 2 && a.rfind("--", 0) == 0) die("unknown flag " + a);
@@ -151,17 +190,21 @@ int main(int argc, char **argv) {
         }
         if (pos.size() != 4) {
             fprintf(stderr, "usage: mtb_build [--add-db OLDDB]... [--cds-info LIST] [--max-records N] [--split-num N] [--syncmer 0|1] [--smer-len n] [--kmer-format 1|2] [--device d] "
-                            "[--validate-db 0|1] GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB\n       mtb_build --audit 1 [--device d] - - TAXONOMYDIR DBDIR\n"
+                            "[--validate-db 0|1] [--inspect 0|1 [--inspect-level dna|aa|both]] GENOMES.fa[.gz] SEQID2TAXID.tsv TAXONOMYDIR OUTDB\n"
+                            "       mtb_build --audit 1 [--device d] - - TAXONOMYDIR DBDIR\n       mtb_build --inspect 1 [--inspect-level dna|aa|both] [--audit 1] [--device d] - - TAXONOMYDIR DBDIR\n"
                             "       mtb_build --add-db DB [--add-db DB2]... [--select-taxid A,B,..] [--exclude-taxid C,..] - - TAXONOMYDIR OUTDB\n");
             return 1;
         }
         const std::string genomes = pos[0], map_path = pos[1], taxdir = pos[2], outdb = pos[3];
-        if (audit_only) {
+        const int inspect_levels = inspect_on ? inspect_level_bits : 0;
+        if (audit_only || (inspect_levels && genomes == "-" && add_db.empty())) {       /* an existing DBDIR: audited, inspected or both */
             mtb_ctx *actx = nullptr;
             chk(mtb_ctx_create(device, nullptr, &actx), "mtb_ctx_create");
-            const mtb_audit_report r = audit(actx, outdb, taxdir, par, true);
+            bool valid = true;
+            if (audit_only) valid = audit(actx, outdb, taxdir, par, true).valid != 0;
+            if (inspect_levels) inspect(actx, outdb, taxdir, par, inspect_levels);
             mtb_ctx_destroy(actx);
-            if (!r.valid) { fprintf(stderr, "Database validation failed.\n"); return 1; }
+            if (!valid) { fprintf(stderr, "Database validation failed.\n"); return 1; }
             return 0;
         }
         if (genomes == "-" && add_db.empty()) die("nothing to build: no genomes and no --add-db");
@@ -349,6 +392,7 @@ int main(int argc, char **argv) {
             sound = audit(ctx, outdb, taxdir, par, false).canonical != 0;
             if (!sound) fprintf(stderr, "mtb_build: %s is not a canonical database\nDatabase validation failed.\n", outdb.c_str());
         }
+        if (inspect_levels) inspect(ctx, outdb, taxdir, par, inspect_levels);
         mtb_ctx_destroy(ctx);
         return sound ? 0 : 1;
     } catch (const std::exception &e) {

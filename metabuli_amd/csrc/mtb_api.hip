@@ -33,6 +33,7 @@
 #include "kernels_clade_filter.h"
 #include "kernels_audit.h"
 #include "kernels_coverage.h"
+#include "kernels_inspect.h"
 #include "kernels_dir.h"
 #include "kernels_scan.h"
 #include "kernels_score.h"
@@ -4737,6 +4738,263 @@ mtb_status mtb_audit_write_species_counts(const char *dbdir, const uint32_t *spe
     if (!f) return fail(MTB_ERR_IO, "cannot create " + path);
     for (uint64_t s = 0; s < n; s++) if (species_counts[s]) fprintf(f, "%llu %u\n", (unsigned long long)s, species_counts[s]);
     if (fclose(f) != 0) return fail(MTB_ERR_IO, "short write to " + path);
+    return MTB_OK;
+}
+
+} // extern "C"
+
+/* ---- inspection of a database: LCA k-mer counts per taxon (mtb.h; kernels_inspect.h; the rule: tests/inspect_spec.py) ---- */
+/* The device passes of one inspection, whoever brings the chunks (decode_chunked's sink, or the stage call's uploads): begin, pass per
+ * chunk in file order, finish.  u32 bins of one pass (distinct, then entries; one array per XCD each), their u64 sums, the counters,
+ * two records per tile, two carry slots used in turn. */
+struct InspectRun {
+    mtb_ctx *c = nullptr;
+    mtb_tax_view tv; uint32_t info_mask = 0; int level = 0;
+    uint64_t n_bins = 0, stride = 0, n_entries = 0, n_passes = 0;
+    uint32_t *d_pass = nullptr; unsigned long long *d_sum = nullptr, *d_out = nullptr;
+    mtb_inspect_rec *d_rec = nullptr, *d_carry = nullptr;
+    int turn = 0; bool any = false;
+    float ms_bins = 0;
+    ~InspectRun() { if (c) for (const char *nm : {"inspbins", "inspsum", "inspout", "insprec", "inspcarry"}) release(c, nm); }
+    uint64_t pass_words() const { return 2 * stride * MTB_AUDIT_REPLICAS; }
+    mtb_status begin(mtb_ctx *c_, const mtb_tax_view &tv_, uint32_t mask, int level_, uint64_t max_pass_entries) {
+        c = c_; tv = tv_; info_mask = mask; level = level_;
+        n_bins = (uint64_t)tv.max_taxid + 1; stride = (n_bins + 63) & ~63ull;
+        const auto t0 = std::chrono::steady_clock::now();
+        STCHK(ensure(c, "inspbins", pass_words(), &d_pass)); STCHK(ensure(c, "inspsum", 2 * n_bins, &d_sum));
+        STCHK(ensure(c, "inspout", (size_t)MTB_INSPECT_WORDS, &d_out)); STCHK(ensure(c, "inspcarry", (size_t)2, &d_carry));
+        STCHK(ensure(c, "insprec", 2 * ((max_pass_entries + MTB_INSPECT_TILE - 1) / MTB_INSPECT_TILE) + 2, &d_rec));
+        hipStream_t st = c->stream;
+        HIPCHK(hipMemsetAsync(d_pass, 0, pass_words() * 4, st)); HIPCHK(hipMemsetAsync(d_sum, 0, 2 * n_bins * 8, st));
+        HIPCHK(hipMemsetAsync(d_carry, 0, 2 * sizeof(mtb_inspect_rec), st));
+        unsigned long long init[MTB_INSPECT_WORDS];
+        for (int k = 0; k < MTB_INSPECT_WORDS; k++) init[k] = 0;
+        init[MTB_INSPECT_WALK_FIRST] = ~0ull;
+        STCHK(h2d(c, d_out, init, sizeof(init)));
+        HIPCHK(hipStreamSynchronize(st));
+        ms_bins += (float)ms_since(t0);
+        return MTB_OK;
+    }
+    /* entries [g0, g0 + m) of the database as a chunk on the device (256-byte aligned); asynchronous on the context's stream */
+    mtb_status pass(const uint64_t *d_values, const uint32_t *d_info, uint64_t m, uint64_t g0) {
+        if (m == 0) return MTB_OK;
+        if (m >> 32) return fail(MTB_ERR_ARG, "a pass of the inspection holds fewer than 2^32 entries");
+        hipStream_t st = c->stream;
+        const uint64_t tiles = (m + MTB_INSPECT_TILE - 1) / MTB_INSPECT_TILE;
+        STCHK(ensure(c, "insprec", 2 * tiles + 2, &d_rec));
+        uint32_t *d_distinct = d_pass, *d_entries = d_pass + stride * MTB_AUDIT_REPLICAS;
+        hipLaunchKernelGGL(k_inspect_tiles, dim3((uint32_t)std::min<uint64_t>(tiles, 4096)), dim3(256), 0, st, d_values, d_info, m, g0, info_mask, level, tv, d_rec, d_distinct, d_entries,
+                           stride, (int)MTB_INSPECT_FOLD_ROUNDS, d_out);
+        hipLaunchKernelGGL(k_inspect_walk, dim3(1), dim3(64), 0, st, (const mtb_inspect_rec *)d_rec, 2 * tiles, (const mtb_inspect_rec *)(d_carry + turn), any ? 1 : 0, d_carry + (turn ^ 1), 0, tv,
+                           d_sum, d_sum + n_bins, (int)MTB_INSPECT_FOLD_ROUNDS, d_out);
+        turn ^= 1; any = true;
+        for (int k = 0; k < 2; k++) {
+            uint32_t *bins = k ? d_entries : d_distinct;
+            hipLaunchKernelGGL(k_audit_bins_reduce, grid256(n_bins), dim3(256), 0, st, bins, n_bins, stride);
+            hipLaunchKernelGGL(k_cov_accumulate, grid256(n_bins), dim3(256), 0, st, d_sum + (uint64_t)k * n_bins, bins, n_bins);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(d_pass + stride, 0, (pass_words() - stride) * 4, st));       /* (k_cov_accumulate cleared the first array; this clears the other replicas and the second set) */
+        n_entries += m; n_passes++;
+        return MTB_OK;
+    }
+    /* closes the last group; the report's counts (not its times), the u64 bins */
+    mtb_status finish(uint64_t *distinct, uint64_t *entries, mtb_inspect_report *R) {
+        hipStream_t st = c->stream;
+        hipLaunchKernelGGL(k_inspect_walk, dim3(1), dim3(64), 0, st, (const mtb_inspect_rec *)d_rec, (uint64_t)0, (const mtb_inspect_rec *)(d_carry + turn), any ? 1 : 0, d_carry + (turn ^ 1), 1, tv,
+                           d_sum, d_sum + n_bins, (int)MTB_INSPECT_FOLD_ROUNDS, d_out);
+        HIPCHK(hipGetLastError());
+        const auto t0 = std::chrono::steady_clock::now();
+        unsigned long long h[MTB_INSPECT_WORDS];
+        STCHK(d2h(c, h, d_out, sizeof(h)));
+        if (distinct) STCHK(d2h(c, distinct, d_sum, n_bins * 8));
+        if (entries) STCHK(d2h(c, entries, d_sum + n_bins, n_bins * 8));
+        ms_bins += (float)ms_since(t0);
+        R->n_entries = n_entries; R->n_chunks = n_passes; R->n_taxa = n_bins;
+        R->n_orphan_groups = h[MTB_INSPECT_ORPHAN_GROUPS]; R->n_orphan_entries = h[MTB_INSPECT_ORPHAN_ENTRIES];
+        R->n_groups = 0;
+        for (int k = 0; k < MTB_INSPECT_HIST; k++) { R->size_hist[k] = h[MTB_INSPECT_HIST0 + k]; R->n_groups += h[MTB_INSPECT_HIST0 + k]; }
+        /* the largest group: among those closed inside a tile and those the walk closed; of equals the first */
+        uint64_t mx = h[MTB_INSPECT_WALK_MAX], first = h[MTB_INSPECT_WALK_FIRST];
+        if (h[MTB_INSPECT_TILE_MAX]) {
+            const uint64_t ts = h[MTB_INSPECT_TILE_MAX] >> 48, tf = MTB_INSPECT_FIRST_MASK - (h[MTB_INSPECT_TILE_MAX] & MTB_INSPECT_FIRST_MASK);
+            if (ts > mx || (ts == mx && tf < first)) { mx = ts; first = tf; }
+        }
+        R->max_group = mx; R->first_max_group = mx ? first : UINT64_MAX;
+        return MTB_OK;
+    }
+};
+
+/* the taxonomy a report is written against: an index's, a database directory's (mtb_database_inspect's rule), or dump files */
+static mtb_status inspect_taxonomy(const mtb_index *ix, const char *dbdir, const char *taxonomy_dir, mtbhost::Taxonomy *own, const mtbhost::Taxonomy **use) {
+    if (ix) { *use = &ix->tax; return MTB_OK; }
+    *use = own;
+    if (dbdir && *dbdir) {
+        const std::string d(dbdir);
+        std::vector<int32_t> ids;
+        return load_database_taxonomy(d, taxonomy_dir && *taxonomy_dir ? std::string(taxonomy_dir) : d + "/taxonomy", mtbhost::file_exists(d + "/taxonomyDB"), own, &ids);
+    }
+    if (!taxonomy_dir || !*taxonomy_dir) return fail(MTB_ERR_ARG, "no taxonomy: an index, a database directory or a taxonomy directory is needed");
+    std::string err;
+    if (!mtbhost::load_taxonomy(taxonomy_dir, own, &err)) return fail(MTB_ERR_IO, err);
+    return MTB_OK;
+}
+
+extern "C" {
+
+uint32_t mtb_inspect_tile_entries(void) { return MTB_INSPECT_TILE; }
+
+mtb_status mtb_database_inspect(mtb_ctx *c, const char *dbdir, const char *taxonomy_dir, mtb_params *params, uint64_t chunk_words, int level, uint64_t *distinct, uint64_t *entries,
+                                uint64_t cap, mtb_inspect_report *out) {
+    if (!c || !dbdir || !params || !out) return fail(MTB_ERR_ARG, "NULL argument");
+    if (level != 0 && level != 1) return fail(MTB_ERR_ARG, "inspection level " + std::to_string(level) + ": 0 (dna) or 1 (aa)");
+    const auto t_all = std::chrono::steady_clock::now();
+    const std::string d(dbdir);
+    /* the files first, as the audit does: nothing below touches the device before they are sound */
+    mtbhost::AuditFiles files;
+    {   std::string err;
+        if (!mtbhost::audit_check_files(d, taxonomy_dir, &files, &err)) return fail(MTB_ERR_IO, d + ": " + err + (files.note.empty() ? "" : " " + files.note)); }
+    auto failed = [&](mtb_status s) { if (!files.note.empty()) g_err += " (" + files.note + ")"; return s; };
+    int reduced_aa = 0;
+    mtbhost::load_db_parameters(d, params, &reduced_aa);
+    if (reduced_aa) return failed(fail(MTB_ERR_UNSUPPORTED, "database was built with the reduced amino-acid alphabet (Reduced_alphabet 1 in db.parameters); not implemented"));
+    if (params->kmer_format != 1 && params->kmer_format != 2) return failed(fail(MTB_ERR_UNSUPPORTED, "database uses a k-mer format other than 1 or 2"));
+    uint64_t trailing = 0;
+    if (!mtbhost::audit_trailing_words(d + "/diffIdx", files.n_words, &trailing)) return failed(fail(MTB_ERR_IO, "cannot read " + d + "/diffIdx"));
+    HIPCHK(hipSetDevice(c->device));
+    mtbhost::Taxonomy tax;
+    std::vector<int32_t> ids;
+    {   const std::string taxdir = taxonomy_dir && *taxonomy_dir ? std::string(taxonomy_dir) : d + "/taxonomy";
+        const mtb_status s = load_database_taxonomy(d, taxdir, mtbhost::file_exists(d + "/taxonomyDB"), &tax, &ids);
+        if (s != MTB_OK) return failed(s); }
+    const uint64_t n_bins = (uint64_t)tax.max_id + 1;
+    if ((distinct || entries) && cap < n_bins) {
+        out->n_taxa = n_bins;
+        return failed(fail(MTB_ERR_CAPACITY, "the arrays hold " + std::to_string(cap) + " entries, the taxonomy needs " + std::to_string(n_bins)));
+    }
+    mtb_index *hold = nullptr;
+    STCHK(tax_holder_index(c, *params, std::move(tax), ids, &hold));
+    struct Guard { mtb_index *ix; ~Guard() { mtb_index_close(ix); } } guard{hold};
+    /* chunk size: the audit's rule */
+    uint64_t CH = chunk_words;
+    if (CH == 0) {
+        CH = decode_chunk_words(c);
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        CH = std::max<uint64_t>(1u << 16, std::min<uint64_t>(CH, (fr + held_bytes(c, BUF_WORK)) / 32));
+    }
+    CH = std::max<uint64_t>(16, std::min<uint64_t>(CH, std::max<uint64_t>(files.n_words, 16)));
+    struct Scratch { mtb_ctx *c; ~Scratch() { for (const char *nm : {"inspv", "inspi"}) release(c, nm); } } scratch{c};
+    DecodeScratch decode_scratch{c};
+    uint64_t *d_v; uint32_t *d_i;
+    STCHK(ensure(c, "inspv", CH + 16, &d_v)); STCHK(ensure(c, "inspi", CH + 16, &d_i));
+    InspectRun run;
+    STCHK(run.begin(c, tax_view(hold), hold->info_mask, level, CH + 16));
+    ChunkSink sink;
+    struct Events { hipEvent_t *e; ~Events() { for (int k = 0; k < 3; k++) if (e[k]) { hipError_t x = hipEventDestroy(e[k]); (void)x; } } } events{sink.ev};
+    for (int k = 0; k < 3; k++) HIPCHK(hipEventCreate(&sink.ev[k]));
+    sink.chunk_words = CH;
+    sink.on_chunk = [&](const DecodedChunk &k) -> mtb_status { return run.pass(k.d_values, k.d_info, k.n_info, k.first_entry); };
+    {   mtbhost::MergeSlice whole;           /* every word before the trailing ones, as the audit reads them */
+        whole.diff_hi = files.n_words - trailing; whole.info_hi = files.n_info_entries;
+        const mtb_status s = decode_chunked(c, params->kmer_format, d, whole, d_v, d_i, nullptr, &sink);
+        if (s != MTB_OK) return failed(s); }
+    mtb_inspect_report R; memset(&R, 0, sizeof(R));
+    {   const mtb_status s = run.finish(distinct, entries, &R);
+        if (s != MTB_OK) return failed(s); }
+    R.n_chunks = sink.n_chunks;
+    R.ms_read = (float)sink.us_read.load() / 1000.0f; R.ms_decode = sink.ms_decode; R.ms_inspect = sink.ms_sink; R.ms_bins = run.ms_bins;
+    R.ms_total = (float)ms_since(t_all);
+    *out = R;
+    return MTB_OK;
+}
+
+mtb_status mtb_inspect_records(mtb_ctx *c, const mtb_index *ix, const char *taxonomy_dir, const uint64_t *values, const uint32_t *info, uint64_t n, uint32_t info_mask, int level,
+                               uint64_t entries_per_pass, uint64_t *distinct, uint64_t *entries, uint64_t cap, mtb_inspect_report *out) {
+    if (!c || !out || (n && (!values || !info))) return fail(MTB_ERR_ARG, "NULL argument");
+    if (level != 0 && level != 1) return fail(MTB_ERR_ARG, "inspection level " + std::to_string(level) + ": 0 (dna) or 1 (aa)");
+    if (ix && ix->ctx->device != c->device) return fail(MTB_ERR_ARG, "the index lives on another device");
+    const auto t_all = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(c->device));
+    mtb_index *hold = nullptr;
+    struct Guard { mtb_index *&ix; ~Guard() { if (ix) mtb_index_close(ix); } } guard{hold};
+    if (!ix) {
+        if (!taxonomy_dir || !*taxonomy_dir) return fail(MTB_ERR_ARG, "no taxonomy: an index or a taxonomy directory is needed");
+        mtbhost::Taxonomy tax; std::string err;
+        if (!mtbhost::load_taxonomy(taxonomy_dir, &tax, &err)) return fail(MTB_ERR_IO, err);
+        mtb_params p; mtb_default_params(&p);
+        STCHK(tax_holder_index(c, p, std::move(tax), std::vector<int32_t>(), &hold));
+    }
+    const mtb_index *t = ix ? ix : hold;
+    const uint64_t n_bins = (uint64_t)t->tax.max_id + 1;
+    if ((distinct || entries) && cap < n_bins) {
+        out->n_taxa = n_bins;
+        return fail(MTB_ERR_CAPACITY, "the arrays hold " + std::to_string(cap) + " entries, the taxonomy needs " + std::to_string(n_bins));
+    }
+    uint64_t P = entries_per_pass ? (entries_per_pass + 3) & ~3ull : std::max<uint64_t>(n, 4);
+    if (P >> 32) P = 1ull << 31;
+    struct Scratch { mtb_ctx *c; ~Scratch() { for (const char *nm : {"inspv", "inspi"}) release(c, nm); } } scratch{c};
+    uint64_t *d_v; uint32_t *d_i;
+    STCHK(ensure(c, "inspv", P + 16, &d_v)); STCHK(ensure(c, "inspi", P + 16, &d_i));
+    InspectRun run;
+    STCHK(run.begin(c, tax_view(t), info_mask, level, P));
+    const auto t0 = std::chrono::steady_clock::now();
+    for (uint64_t g0 = 0; g0 < n; g0 += P) {
+        const uint64_t m = std::min<uint64_t>(P, n - g0);
+        STCHK(h2d(c, d_v, values + g0, m * 8)); STCHK(h2d(c, d_i, info + g0, m * 4));
+        STCHK(run.pass(d_v, d_i, m, g0));
+        HIPCHK(hipStreamSynchronize(c->stream));          /* the chunk buffers are refilled next */
+    }
+    mtb_inspect_report R; memset(&R, 0, sizeof(R));
+    STCHK(run.finish(distinct, entries, &R));
+    R.ms_inspect = (float)ms_since(t0); R.ms_bins = run.ms_bins; R.ms_total = (float)ms_since(t_all);
+    *out = R;
+    return MTB_OK;
+}
+
+mtb_status mtb_inspect_write_report(const mtb_index *ix, const char *dbdir, const char *taxonomy_dir, const uint64_t *distinct, const uint64_t *entries, uint64_t n, uint64_t n_groups,
+                                    const char *tsv_path, char *summary, uint64_t summary_cap) {
+    if (!distinct || !entries) return fail(MTB_ERR_ARG, "NULL argument");
+    mtbhost::Taxonomy own; const mtbhost::Taxonomy *tax = nullptr;
+    STCHK(inspect_taxonomy(ix, dbdir, taxonomy_dir, &own, &tax));
+    const uint64_t n_bins = (uint64_t)tax->max_id + 1;
+    if (n < n_bins) return fail(MTB_ERR_CAPACITY, "the arrays hold " + std::to_string(n) + " entries, the taxonomy needs " + std::to_string(n_bins));
+    auto node = [&](uint64_t t) { return tax->canon[t] == (int32_t)t; };
+    if (tsv_path) {
+        /* clade sums: children before parents, by descending depth */
+        std::vector<uint64_t> dc(distinct, distinct + n_bins), ec(entries, entries + n_bins);
+        std::vector<int32_t> order;
+        for (uint64_t t = 0; t < n_bins; t++) if (node(t)) order.push_back((int32_t)t);
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return tax->depth[(size_t)a] > tax->depth[(size_t)b]; });
+        for (int32_t t : order) {
+            const int32_t p = tax->parent[(size_t)t];
+            if (p != t && p >= 0) { dc[(size_t)p] += dc[(size_t)t]; ec[(size_t)p] += ec[(size_t)t]; }
+        }
+        FILE *f = fopen(tsv_path, "w");
+        if (!f) return fail(MTB_ERR_IO, std::string("cannot create ") + tsv_path);
+        fprintf(f, "original_taxid\trank\tname\tdistinct\tentries\tdistinct_clade\tentries_clade\n");
+        for (uint64_t t = 0; t < n_bins; t++) {
+            if (!node(t) || (!dc[t] && !ec[t])) continue;
+            fprintf(f, "%d\t%s\t%s\t%llu\t%llu\t%llu\t%llu\n", tax->orig.empty() ? (int)t : (int)tax->orig[t], tax->rank[t].c_str(), tax->name[t].c_str(), (unsigned long long)distinct[t],
+                    (unsigned long long)entries[t], (unsigned long long)dc[t], (unsigned long long)ec[t]);
+        }
+        if (fclose(f) != 0) return fail(MTB_ERR_IO, std::string("short write to ") + tsv_path);
+    }
+    if (summary) {
+        static const char *const order[] = {"root", "superkingdom", "phylum", "class", "order", "family", "genus", "species", "subspecies", "no rank"};      /* count_common_kmers.cpp:107-109 */
+        auto by_rank = [&](const uint64_t *arr) {
+            std::map<std::string, uint64_t> sum;
+            for (uint64_t t = 0; t < n_bins; t++) if (node(t) && arr[t]) sum[t == 1 ? std::string("root") : tax->rank[t]] += arr[t];
+            std::string s;
+            for (const char *r : order) { auto it = sum.find(r); if (it != sum.end()) { s += it->first + ": " + std::to_string(it->second) + "\n"; sum.erase(it); } }
+            for (const auto &kv : sum) s += kv.first + ": " + std::to_string(kv.second) + "\n";      /* (the reference drops these; a map walks them alphabetically) */
+            return s;
+        };
+        const std::string s = "Common k-mers count by rank:\n" + by_rank(entries) + "Total distinct common k-mers count: " + std::to_string(n_groups) + "\n" +
+                              "Distinct common k-mers count by rank:\n" + by_rank(distinct);
+        if (s.size() + 1 > summary_cap) return fail(MTB_ERR_CAPACITY, "the summary needs " + std::to_string(s.size() + 1) + " bytes");
+        memcpy(summary, s.c_str(), s.size() + 1);
+    }
     return MTB_OK;
 }
 
