@@ -116,6 +116,11 @@ typedef struct {
     int32_t  join_variant, join_tuned;
     float    join_tune_ms[3];
     uint32_t join_tiles, join_tiles_windowed, join_tiles_outside;
+    /* long reads on per-read slot ranges (score_long_slots): the tail factor the (last sub-)batch was scored with -- 1 = tails of a quarter of
+     * the read's metamers, 4 = of all of them; 0 = the slot ranges did not score it (short reads, MTB_NO_LONG_SLOTS, or the tails overflowed
+     * at 4 and the range was redone on exact segments) -- and the reads k_seg_order put on its fail list (more tail matches or candidate
+     * species than its LDS tables hold), which were copied to exact segments, sorted the general way and scored by a second launch */
+    uint32_t lslot_tail_factor, n_lslot_big_reads;
 } mtb_batch_stats;
 
 /* the exact instantiations of the short-read join (kernels_dir.h) */

@@ -2827,6 +2827,7 @@ static mtb_status score_long_slots(mtb_ctx *c, mtb_index *ix, const mtb_params *
             STCHK(h2d(c, scal<uint64_t>(c, SC_N_GENERIC), &n_generic, 8));
         }
         *nm_out = sc2[1] + big_total; *done = true;
+        c->stats.lslot_tail_factor = tf; c->stats.n_lslot_big_reads = n_failed;
     }
     return MTB_OK;
 }
@@ -2964,6 +2965,7 @@ static void merge_stats(mtb_batch_stats &S, const mtb_batch_stats &L) {
     S.join_variant = L.join_variant; S.join_tuned = L.join_tuned;                 /* (of the last range) */
     for (int v = 0; v < 3; v++) S.join_tune_ms[v] = L.join_tune_ms[v];
     S.join_tiles += L.join_tiles; S.join_tiles_windowed += L.join_tiles_windowed; S.join_tiles_outside += L.join_tiles_outside;
+    S.lslot_tail_factor = L.lslot_tail_factor; S.n_lslot_big_reads += L.n_lslot_big_reads;       /* (factor: of the last range) */
 }
 
 /* HBM-budgeted batching (the reference sizes a QuerySplit from --max-ram, QueryIndexer.cpp:62,132, and redoes

@@ -107,6 +107,17 @@ def test_long_reads_and_long_runs_on_the_emulator(emulated_lib):
                        "or (test_runs_of_a_dozen_candidates_inside_and_outside_a_window and 11)")
 
 
+def test_long_read_slot_routing_on_the_emulator(emulated_lib):
+    """the long-read slot path at its table and tail edges (tests/test_gpu_long_slots.py): 768 / 769 candidate species and 2048 / 2049 tail
+    matches around k_seg_order's LDS tables, the tail cursor at and one above the slot range for tail factors 1 and 4 (escalation, its
+    stickiness, the redo on exact segments), the wave quarters' step edges, bucket collisions with dropped markers in the probe chains,
+    640 reads on 512 workgroups -- each routed as the mirrored plan says (lslot_tail_factor, n_lslot_big_reads) and equal to the oracle.
+    Logic only: the atomics, wave barriers and work stealing are the GPU run's; the noisy-read case stays there too."""
+    ids = ["species-768", "species-769", "tail-2048", "tail-2049", "tf1-full", "tf1-over", "tf4-full", "tf4-over", "test_quarters", "test_bloom_collision", "test_loop_640"]
+    tail = _run(emulated_lib, " or ".join(ids), module="test_gpu_long_slots.py")
+    assert f"{len(ids)} passed" in tail, tail               # (every id selected a case: none renamed away silently)
+
+
 def test_join_past_the_last_target_on_the_emulator(emulated_lib):
     """the window form of the directory join on an index cut to its first 15 % of targets (tests/test_gpu_join_edges.py): queries whose bucket
     lies past the last target, in tiles staged in LDS, must not take the words before the end as candidates; next to it the sector-random form"""
