@@ -308,27 +308,40 @@ class ReadScorer:
             # predecessors come first in list order, compared from the end match backwards
             best = max(cands, key=lambda c: (c[0], tuple(-x for x in c[1])))
             if best[3] >= min_depth:
+                # multi_pred / tied_chains change no result: what a designed read's precondition reads (tests/designed_reads.py)
                 emitted.append(dict(start=block[best[4]][0] & 0xFFFFFFFF, end=(block[i][0] & 0xFFFFFFFF) + 23, score=np.float32(best[0]),
-                                    ham=best[2], depth=best[3], start_match=block[best[4]], end_match=block[i]))
+                                    ham=best[2], depth=best[3], start_match=block[best[4]], end_match=block[i],
+                                    multi_pred=any(len(preds[j]) >= 2 for j in best[1]),
+                                    tied_chains=sum(1 for c in cands if c[0] == best[0]) >= 2))
         return emitted
 
     # -- a16 ------------------------------------------------------------------------------------------
     @staticmethod
-    def combine(paths, read_len):
+    def combine(paths, read_len, trace=None):
+        """trace: a list that receives one dict per candidate in sorted order -- the branches it took against the accepted paths
+        (("left" | "right", ov % 3) per trim), drop = None | "inside" | "ge24", against = index of the accepted path that dropped it,
+        equal_key = its (score, hamming, start) equals the previous candidate's.  Changes no result."""
         paths = sorted(paths, key=lambda p: (-float(p["score"]), p["ham"], -p["start"]))       # stable, like a small std::sort
         acc = []
         total = np.float32(0)
+        prev_key = None
         for p in paths:
             p = dict(p)
             drop = False
-            for c in acc:
+            t = dict(trims=[], drop=None, against=None, equal_key=prev_key == (float(p["score"]), p["ham"], p["start"]))
+            prev_key = (float(p["score"]), p["ham"], p["start"])
+            if trace is not None:
+                trace.append(t)
+            for ci, c in enumerate(acc):
                 if p["end"] < c["start"] or c["end"] < p["start"]:
                     continue
                 ov = min(p["end"], c["end"]) - max(p["start"], c["start"]) + 1
                 if ov == p["end"] - p["start"] + 1 or ov >= 24:
                     drop = True
+                    t["drop"], t["against"] = ("inside" if ov == p["end"] - p["start"] + 1 else "ge24"), ci
                     break
                 k = ov // 3
+                t["trims"].append(("left" if p["start"] < c["start"] else "right", ov % 3))
                 if p["start"] < c["start"]:
                     reh = p["end_match"][4]
                     p["end"] = c["start"] - 1
@@ -380,7 +393,10 @@ class ReadScorer:
             root = best[0]
 
     def score_read(self, matches, qlen, qlen2):
-        """matches of one read in compareMatches order -> (classification, score f32, is_classified, taxcnt dict)"""
+        """matches of one read in compareMatches order -> (classification, score f32, is_classified, taxcnt dict).
+        self.last keeps what the decision went through (per species: emitted paths, combine trace, capped score before min_score;
+        the tied list) for the preconditions of tests/designed_reads.py."""
+        self.last = dict(species=[], tied=[])
         read_len = qlen + qlen2
         sp2score = []
         best_sp, best_range, meaningful = np.float32(0), None, 0
@@ -397,7 +413,10 @@ class ReadScorer:
                 paths += self.block_paths(matches[b:i], sp)
             if not paths:
                 continue
-            sc = min(self.combine(paths, read_len), np.float32(1.0))
+            trace = []
+            raw = self.combine(paths, read_len, trace)
+            sc = min(raw, np.float32(1.0))
+            self.last["species"].append(dict(species=sp, paths=paths, trace=trace, raw=raw, score=sc))
             if sc < self.min_score:
                 continue
             sp2score.append((sp, sc))
@@ -408,6 +427,7 @@ class ReadScorer:
         if meaningful == 0:
             return 0, np.float32(0), 0, {}
         tied = [(sp, sc) for sp, sc in sp2score if sc >= np.float32(best_sp * self.tie_ratio)]
+        self.last["tied"] = tied
         score = np.float32(0)
         for _, sc in tied:
             score = np.float32(score + sc)

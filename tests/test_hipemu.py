@@ -118,6 +118,15 @@ def test_long_read_slot_routing_on_the_emulator(emulated_lib):
     assert f"{len(ids)} passed" in tail, tail               # (every id selected a case: none renamed away silently)
 
 
+def test_designed_reads_on_the_emulator(emulated_lib):
+    """designed reads on the edges of the scoring rules (tests/test_gpu_designed_reads.py): the ties (LCA at genus, Bacteria and root; equal
+    scores at tie_ratio = 1; deferred when the species share the read's metamers, decided by k_score_fast when they do not), one species emitting 16 | 17 and 64 | 65 paths (the 65-path read is the one k_score_fast hands over) and the
+    frame changes that drive the combination through its trims and drops -- through the exact segments of k_score and the fused batch with
+    and without the register-resident scorer, each routed as the mirrored plan says."""
+    tail = _run(emulated_lib, "[Ties] or [DisjointTies] or [ManyPaths] or [Combine]", module="test_gpu_designed_reads.py")
+    assert "8 passed" in tail, tail                         # (four cases through two tests: none renamed away silently)
+
+
 def test_join_past_the_last_target_on_the_emulator(emulated_lib):
     """the window form of the directory join on an index cut to its first 15 % of targets (tests/test_gpu_join_edges.py): queries whose bucket
     lies past the last target, in tiles staged in LDS, must not take the words before the end as candidates; next to it the sector-random form"""
