@@ -32,7 +32,7 @@
 
 #define MTB_FAST_BKT 128          /* position buckets handled in LDS */
 #ifndef MTB_FAST_MERGE_SINGLES
-#define MTB_FAST_MERGE_SINGLES 0  /* A/B switch (make libmtb_xmerge.so X=-DMTB_FAST_MERGE_SINGLES=1): the tail merge for single reads too */
+#define MTB_FAST_MERGE_SINGLES 1  /* the tail merge for single reads too; A/B: make libmtb_xhandover.so X=-DMTB_FAST_MERGE_SINGLES=0 hands such reads to k_score<SLOT> */
 #endif
 
 /* debugging build only (-DMTB_FAST_DEBUG): why reads leave the fast path: 0 tail overflow / buckets, 1 > 8 species, 2 not sorted
@@ -220,57 +220,78 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
             bool any_tail = false;
 #pragma unroll
             for (int k = 0; k < KL; k++) any_tail |= live[k] && (uint32_t)lane + 64u * k >= direct;
-            /* pairs only: there the generic kernel costs 20 ns per read it takes over (320-record staging, 2 waves per SIMD), and the merge
-             * pays (12.5 M pairs: generic 21.5 -> 6.8 ms, this kernel 72 -> 77 ms); single reads lose (generic 2.9 -> 0.9 ms, this kernel
-             * 22.5 -> 26.5 ms: the merge costs about what the read's whole scoring does) and keep handing such reads over */
+            /* Pairs: the generic kernel costs 20 ns per read it takes over (320-record staging, 2 waves per SIMD), and the merge pays
+             * (12.5 M pairs: generic 21.5 -> 6.8 ms, this kernel 72 -> 77 ms).  Single reads: with the serial merge (a wave step per tail match:
+             * 2 K ballots and a loop over the other tail matches) they lost -- generic 6.4 -> 1.3 ms, this kernel 17.3 -> 22.4 ms per 10 M
+             * reads, 9.7 % of them with tail matches -- and handed such reads over.  With the merge below (a lane per tail match) this kernel
+             * goes 17.25 -> 21.3 ms and the generic one 6.4 -> 1.3 ms, and the score stage comes out 1.8 ms ahead
+             * (profiles/score_tiers_notes.md).  The 4 ms are SUPPOSED to be mostly the scoring of those reads itself (two or three species
+             * each) and not the merge: the split has not been measured (the MTB_FAST_DEBUG phase marks would give it) */
             if ((BYFRAME || MTB_FAST_MERGE_SINGLES) && !slow && __any(any_tail)) {
                 FKey ke[K]; uint64_t ax[K]; int32_t np[K]; bool tl[K];
                 const int32_t nsl = (n + 63) >> 6;
+                auto same_run = [&](const FKey &a, const FKey &b) { return BYFRAME ? ((a.hi ^ b.hi) >> 7) == 0 : ((a.hi ^ b.hi) >> 10) == 0; };
+                auto less = [&](const FKey &a, const FKey &b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); };
+                /* The merge is computed in parallel: tail match t on lane t finds its place by bisection over its run's direct matches, a direct
+                 * match counts the tail matches it moves behind.  That needs every run's direct matches in nondecreasing key order among
+                 * themselves (out of order, two records could land on one place and the S1 check below would never see the lost one): a
+                 * direct match is compared with the one before it, and a read that fails goes to the generic kernel. */
+                bool unsorted = false;
 #pragma unroll
                 for (int k = 0; k < K; k++) {
                     const int32_t i = lane + 64 * k;
                     ke[k].lo = 0; ke[k].hi = 0; ax[k] = 0; np[k] = i; tl[k] = false;
-                    if (k < nsl && i < n) { ke[k] = s_key[i]; ax[k] = s_aux[i]; tl[k] = (ax[k] >> 63) != 0; }
+                    if (k < nsl && i < n) {
+                        ke[k] = s_key[i]; ax[k] = s_aux[i]; tl[k] = (ax[k] >> 63) != 0;
+                        if (i > 0 && !tl[k]) { const FKey pk = s_key[i - 1]; if ((s_aux[i - 1] >> 63) == 0 && same_run(pk, ke[k]) && less(ke[k], pk)) unsorted = true; }
+                    }
                     if (k < nsl) {
                         const uint64_t tm = __ballot(tl[k]);
                         if (tl[k]) { const uint32_t at = nt + (uint32_t)__popcll(tm & lt); if (at < 64u) s_tl[at] = (uint32_t)i; }
                         nt += (uint32_t)__popcll(tm);
                     }
                 }
-                if (nt > 64u) slow = true;
+                if (nt > 64u || __any(unsorted)) slow = true;
                 wave_fence();
                 if (!slow) {
-                    auto same_run = [&](const FKey &a, const FKey &b) { return BYFRAME ? ((a.hi ^ b.hi) >> 7) == 0 : ((a.hi ^ b.hi) >> 10) == 0; };
-                    auto less = [&](const FKey &a, const FKey &b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); };
-                    for (uint32_t t = 0; t < nt; t++) {
-                        const int32_t ti = (int32_t)s_tl[t];
-                        const FKey kt = s_key[ti];
-                        /* direct matches of the run: those with a greater key move one place back; counts for the tail match itself */
-                        uint32_t n_dir_less = 0, n_dir_run = 0;
+                    const bool mine = (uint32_t)lane < nt;                     /* lane t owns tail match t */
+                    const int32_t ti = mine ? (int32_t)s_tl[lane] : 0;
+                    const FKey kt = s_key[ti]; const uint64_t at = s_aux[ti];
+                    uint32_t n_tl_run = 0, n_tl_less = 0;
+                    for (uint32_t u = 0; u < nt; u++) {
+                        FKey ku; ku.hi = (uint32_t)rl_i((int32_t)kt.hi, (int32_t)u); ku.lo = (uint32_t)rl_i((int32_t)kt.lo, (int32_t)u);
+                        /* equal keys: tail order breaks the tie, and a direct match counts a tail match of equal key as before it (`!less` in the
+                         * loop below), so two records never share a place.  DEFENSIVE ONLY: a database holds one entry per value and species, two
+                         * matches of a read cannot agree in species, frame, position, hamming and dna, and no test reaches these two rules */
+                        if (same_run(ku, kt)) { n_tl_run++; n_tl_less += (less(ku, kt) || (!less(kt, ku) && u < (uint32_t)lane)) ? 1u : 0u; }
 #pragma unroll
-                        for (int k = 0; k < K; k++) {
-                            if (k < nsl) {
-                                const int32_t i = lane + 64 * k;
-                                const bool dir = i < n && !tl[k] && same_run(ke[k], kt);
-                                const bool smaller = dir && less(ke[k], kt);
-                                if (dir && !smaller) np[k]++;
-                                n_dir_run += (uint32_t)__popcll(__ballot(dir)); n_dir_less += (uint32_t)__popcll(__ballot(smaller));
-                            }
-                        }
-                        uint32_t n_tl_less = 0, n_tl_before = 0;
-                        for (uint32_t u = 0; u < nt; u++) {
-                            if (u == t) continue;
-                            const FKey ku = s_key[s_tl[u]];
-                            if (!same_run(ku, kt)) continue;
-                            n_tl_less += (less(ku, kt) || (!less(kt, ku) && u < t)) ? 1u : 0u; n_tl_before += u < t ? 1u : 0u;      /* equal keys (one metamer value in several targets of a species): tail order breaks the tie, two records never share a place */
-                        }
-                        const int32_t run_start = ti - (int32_t)n_dir_run - (int32_t)n_tl_before;
-#pragma unroll
-                        for (int k = 0; k < K; k++) if (lane + 64 * k == ti) np[k] = run_start + (int32_t)(n_dir_less + n_tl_less);
+                        for (int k = 0; k < K; k++)                              /* a direct match moves behind the tail matches of its run that are not greater */
+                            if (k < nsl && !tl[k] && same_run(ke[k], ku) && !less(ke[k], ku)) np[k]++;
                     }
+                    /* the run of tail match t: [run_start, run_end) by two bisections on the run id (the runs are in ascending order), its direct
+                     * matches are the first n_dir_run of it; then the direct matches with a smaller key (strict: a tail match goes before a
+                     * direct match of equal key, which counted it above) */
+                    const uint32_t rid = BYFRAME ? kt.hi >> 7 : kt.hi >> 10;
+                    int32_t lo0 = 0, hi0 = n, lo1 = 0, hi1 = n;
+                    for (int32_t len = n; len; len >>= 1) {
+                        const int32_t m0 = (lo0 + hi0) >> 1, m1 = (lo1 + hi1) >> 1;
+                        const uint32_t r0 = BYFRAME ? s_key[m0 < n ? m0 : 0].hi >> 7 : s_key[m0 < n ? m0 : 0].hi >> 10;
+                        const uint32_t r1 = BYFRAME ? s_key[m1 < n ? m1 : 0].hi >> 7 : s_key[m1 < n ? m1 : 0].hi >> 10;
+                        if (lo0 < hi0) { if (r0 < rid) lo0 = m0 + 1; else hi0 = m0; }
+                        if (lo1 < hi1) { if (r1 <= rid) lo1 = m1 + 1; else hi1 = m1; }
+                    }
+                    const int32_t run_start = lo0, n_dir_run = lo1 - lo0 - (int32_t)n_tl_run;
+                    int32_t lo2 = run_start, hi2 = run_start + n_dir_run;
+                    for (int32_t len = n; len; len >>= 1) {
+                        const int32_t m2 = (lo2 + hi2) >> 1;
+                        const FKey km = s_key[m2 < n ? m2 : 0];
+                        if (lo2 < hi2) { if (less(km, kt)) lo2 = m2 + 1; else hi2 = m2; }
+                    }
+                    const int32_t place = lo2 + (int32_t)n_tl_less;          /* run_start + n_dir_less + n_tl_less */
                     wave_fence();
 #pragma unroll
-                    for (int k = 0; k < K; k++) { const int32_t i = lane + 64 * k; if (k < nsl && i < n) { s_key[np[k]] = ke[k]; s_aux[np[k]] = ax[k] & ~(1ull << 63); } }
+                    for (int k = 0; k < K; k++) { const int32_t i = lane + 64 * k; if (k < nsl && i < n && !tl[k]) { s_key[np[k]] = ke[k]; s_aux[np[k]] = ax[k]; } }
+                    if (mine) { s_key[place] = kt; s_aux[place] = at & ~(1ull << 63); }
                     wave_fence();
                 }
             }

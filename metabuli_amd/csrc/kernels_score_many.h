@@ -15,13 +15,16 @@
  * the read's slot segment (direct + tail slots) and its entries of the overflow list, grouped by read by k_ovf_group:
  *   pass 1  every live record enters its species into an open-addressing table in LDS (atomicCAS on the key) and marks its frame:
  *           bit f = "a match in frame f", bit 8 + f = "a second match in frame f" (two atomicOr);
- *   pass 2  the records are read again (L2 hits), those of species with any "second match" bit are staged in LDS in encounter order;
+ *   pass 2  the records are taken again (stride <= 192: from the registers pass 1 loaded them into, slots and the first 128 overflow
+ *           entries; else read again, L2 hits), those of species with any "second match" bit are staged in LDS in encounter order;
  *   then    the generic per-read phases (score_read_par, kernels_score.h: rank sort on the 64-bit compareMatches key, paths,
  *           combination, decision, filter, taxCnt, descent) run on the survivors -- a list of the size of an ordinary read.
  * Reads it cannot take (survivors beyond the staging, species table full, reads routed around their slots, too many position buckets)
  * are listed for the exact-segment path, which stays as the catch-all.
  * The table lives in the part of the scoring workspace that pass 2 does not write (everything behind the match records).
- * Algorithmic HBM bytes: 16 per slot + 24 per overflow entry, read twice (the second time from L2), + 24 per read result.      */
+ * Algorithmic HBM bytes: 16 per slot + 24 per overflow entry (stride > 192: read twice, the second time from L2), + 24 per read result.
+ * Requesting the next read's record lines while the current one is scored (the landing-zone prefetch of k_score_fast) gained 0.2 ms of
+ * 11.8, less than three times the run-to-run spread: not kept (profiles/experiments/score_many_next_read_prefetch.patch).          */
 #ifndef MTB_KERNELS_SCORE_MANY_H
 #define MTB_KERNELS_SCORE_MANY_H
 #include "dev_util.h"
@@ -224,17 +227,36 @@ __global__ __launch_bounds__(64, (CAP > 192 ? 2 : 3)) void k_score_many(const mt
     /* reads differ a lot (a few dozen to a thousand records): claimed from a counter, MTB_MANY_CLAIM list entries per atomic -- one
      * returning atomic per read on ONE address was ~19 ns each once 3000 waves hammer it: 15 of the kernel's 30 ms for 0.8 M reads */
     for (uint64_t c0 = (uint64_t)__shfl(lane == 0 ? atomicAdd(work, (unsigned long long)MTB_MANY_CLAIM) : 0ull, 0, 64); c0 < n_iter;
-         c0 = (uint64_t)__shfl(lane == 0 ? atomicAdd(work, (unsigned long long)MTB_MANY_CLAIM) : 0ull, 0, 64))
-    for (uint64_t it = c0; it < c0 + MTB_MANY_CLAIM && it < n_iter; it++) {
-        const uint64_t r = (uint64_t)list[it];
-        const int32_t ql1 = qlen[r], ql2 = qlen2[r];
+         c0 = (uint64_t)__shfl(lane == 0 ? atomicAdd(work, (unsigned long long)MTB_MANY_CLAIM) : 0ull, 0, 64)) {
+    /* the headers of the claimed block, one read per lane: two dependent round trips per MTB_MANY_CLAIM reads instead of two per read
+     * (list entry -> lengths, cursor, overflow range); the reads' loop takes them with readlane */
+    const uint32_t n_blk = (uint32_t)(n_iter - c0 < (uint64_t)MTB_MANY_CLAIM ? n_iter - c0 : (uint64_t)MTB_MANY_CLAIM);
+    /* h_nov = ~0: a read routed around its slots; h_ql = the mates' used lengths in 16 bits each.  Lossless: a batch takes the slot path
+     * only if EVERY read of it, the routed ones included, is shorter than 65533 bases (classify_attempt: max_len + 3 < 65536 on either slot
+     * layout, else the batch is extracted again for exact segments and this kernel does not run); the clamp below only keeps the
+     * packing well defined */
+    uint32_t h_r = 0, h_cur = 0, h_nov = 0, h_ql = 0; uint64_t h_o0 = 0;
+    if (lane < n_blk) {
+        h_r = list[c0 + lane];
+        const uint32_t q1 = (uint32_t)qlen[h_r], q2 = (uint32_t)qlen2[h_r];
+        h_ql = (q1 < 65535u ? q1 : 65535u) | ((q2 < 65535u ? q2 : 65535u) << 16); h_cur = cursor[h_r];
+        uint64_t o1 = 0; uint8_t routed = 0;
+        if (ovf_start) { h_o0 = ovf_start[h_r]; o1 = ovf_start[(uint64_t)h_r + 1]; }
+        if (off_reads) routed = off_reads[h_r];
+        h_nov = routed ? 0xFFFFFFFFu : (uint32_t)(o1 - h_o0);
+    }
+    auto rl_u64 = [](uint64_t v, int32_t l) { return (uint64_t)(uint32_t)rl_i((int32_t)(uint32_t)v, l) | ((uint64_t)(uint32_t)rl_i((int32_t)(uint32_t)(v >> 32), l) << 32); };
+    for (uint32_t j = 0; j < n_blk; j++) {
+        const uint64_t r = (uint64_t)(uint32_t)rl_i((int32_t)h_r, (int32_t)j);
+        const uint32_t qlp = (uint32_t)rl_i((int32_t)h_ql, (int32_t)j);
+        const int32_t ql1 = (int32_t)(qlp & 0xFFFFu), ql2 = (int32_t)(qlp >> 16);
         const int32_t read_len = ql1 + ql2;
         const int32_t nb = mtb_num_buckets(read_len, sp.dna_shift);
-        const uint32_t cur = cursor[r];
+        const uint32_t cur = (uint32_t)rl_i((int32_t)h_cur, (int32_t)j);
         const uint32_t tail_n = cur < tail_cap ? cur : tail_cap;
-        uint64_t o0 = 0; uint32_t n_ov = 0;
-        if (ovf_start) { o0 = ovf_start[r]; n_ov = (uint32_t)(ovf_start[r + 1] - o0); }
-        bool hand_on = (off_reads && off_reads[r]) || nb > MTB_SCORE_BKT || cur - tail_n != n_ov;
+        const uint64_t o0 = rl_u64(h_o0, (int32_t)j);
+        const uint32_t n_ov = (uint32_t)rl_i((int32_t)h_nov, (int32_t)j);
+        bool hand_on = n_ov == 0xFFFFFFFFu || nb > MTB_SCORE_BKT || cur - tail_n != n_ov;
         uint32_t why = 2;
         /* a read with more than three times the staging in its tail + overflow entries alone (a conserved gene of an organism that is NOT in the
          * index: ~1100 records over a thousand species, most of them with a pair of matches -- the dead-species drop barely shrinks it) would
@@ -245,9 +267,31 @@ __global__ __launch_bounds__(64, (CAP > 192 ? 2 : 3)) void k_score_many(const mt
         mtb_sws<uint16_t> w;
         mtb_sws_carve<uint16_t>(&w, s_ws, CAP);
         uint32_t n = 0, n_all = 0;
+        /* stride <= 192 (what the 192-record staging is chosen for): the read's slots and its first 128 overflow entries are loaded ONCE, every
+         * load in flight before the first is used, and stay in registers for both passes (before: a dependent round trip per 64 records
+         * and pass, the second pass out of L2) */
+        constexpr bool REGS = CAP <= 192;
+        const bool in_regs = REGS && stride <= 192u;
+        uint64_t xa[REGS ? 3 : 1], xb[REGS ? 3 : 1], ow[REGS ? 2 : 1][3];      /* slots (words a, b); overflow entries as the three words of their record */
+        auto ow_species = [](const uint64_t *w_) { return (uint32_t)(w_[1] >> 32); };
+        static_assert(sizeof(mtb_match) == 24 && offsetof(mtb_match, species_id) == 12 && offsetof(mtb_match, pad) == 23, "overflow entries are read as three 64-bit words");
         if (!hand_on) {
+            if constexpr (REGS) if (in_regs) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) { const uint32_t i = lane + 64u * k; xa[k] = 0; xb[k] = 0; if (i < stride) { const mtb_slot16 x = slots[i]; xa[k] = x.a; xb[k] = x.b; } }
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const uint32_t i = lane + 64u * k;
+                    ow[k][0] = 0; ow[k][1] = 0; ow[k][2] = 0;
+                    if (i < n_ov) { const uint64_t *q = (const uint64_t *)(ovfg + o0 + i); ow[k][0] = q[0]; ow[k][1] = q[1]; ow[k][2] = q[2]; }
+                }
+            }
             score_sync<uint16_t>();                      /* the previous read is through with the workspace */
-            for (uint32_t q = lane; q < MTB_MANY_HASH; q += 64) { h_key[q] = 0xFFFFFFFFu; h_val[q] = 0u; }
+            {   /* keys 0xFFFFFFFF, values 0: the two halves of one 8 KB block, 16 bytes per store */
+                uint4 *const tb = (uint4 *)h_key;
+                const uint4 ones = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu), zero = make_uint4(0u, 0u, 0u, 0u);
+                for (uint32_t q = lane; q < MTB_MANY_HASH / 4u; q += 64) { tb[q] = ones; tb[q + MTB_MANY_HASH / 4u] = zero; }
+            }
             if (lane == 0) s_tfull = 0;
             score_sync<uint16_t>();
             bool full = false;
@@ -266,6 +310,19 @@ __global__ __launch_bounds__(64, (CAP > 192 ? 2 : 3)) void k_score_many(const mt
                 }
                 full = true; s_tfull = 1;
             };
+            if constexpr (REGS) if (in_regs) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    const uint32_t i = lane + 64u * k;
+                    mtb_slot16 x; x.a = xa[k]; x.b = xb[k];
+                    const bool live = i < stride && seg_slot_live(x, i, direct, tail_n, epoch);
+                    if (live) enter((uint32_t)(x.a >> 32), (uint32_t)(x.b >> 52) & 7u);
+                    n_all += (uint32_t)__popcll(__ballot(live));
+                }
+#pragma unroll
+                for (int k = 0; k < 2; k++) if (lane + 64u * k < n_ov) enter(ow_species(ow[k]), mtb_q_frame(ow[k][0]));
+            }
+            if (!in_regs)
             for (uint32_t c0 = 0; c0 < stride; c0 += 64) {
                 const uint32_t i = c0 + lane;
                 mtb_slot16 x; x.a = 0; x.b = 0;
@@ -274,7 +331,7 @@ __global__ __launch_bounds__(64, (CAP > 192 ? 2 : 3)) void k_score_many(const mt
                 if (live) enter((uint32_t)(x.a >> 32), (uint32_t)(x.b >> 52) & 7u);
                 n_all += (uint32_t)__popcll(__ballot(live));
             }
-            for (uint32_t c0 = 0; c0 < n_ov; c0 += 64) {
+            for (uint32_t c0 = in_regs ? 128u : 0u; c0 < n_ov; c0 += 64) {
                 const uint32_t i = c0 + lane;
                 if (i < n_ov) { const mtb_match m = ovfg[o0 + i]; enter((uint32_t)m.species_id, mtb_q_frame(m.qinfo)); }
             }
@@ -302,6 +359,29 @@ __global__ __launch_bounds__(64, (CAP > 192 ? 2 : 3)) void k_score_many(const mt
                     const uint64_t *q = (const uint64_t *)&m;
                     dst64[3 * pos] = q[0]; dst64[3 * pos + 1] = q[1]; dst64[3 * pos + 2] = q[2];
                 };
+                if constexpr (REGS) if (in_regs) {       /* the same encounter order as the loops: slots, then overflow entries */
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        const uint32_t i = lane + 64u * k;
+                        mtb_slot16 x; x.a = xa[k]; x.b = xb[k];
+                        const bool keep = i < stride && seg_slot_live(x, i, direct, tail_n, epoch) && alive((uint32_t)(x.a >> 32));
+                        const uint64_t mask = __ballot(keep);
+                        const uint32_t pos = n + (uint32_t)__popcll(mask & lt);
+                        if (keep && pos < (uint32_t)CAP) put(pos, mtb_slot_unpack(x, (uint32_t)r + 1));
+                        n += (uint32_t)__popcll(mask);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 2; k++) {
+                        if (64u * k < n_ov) {
+                            const bool keep = lane + 64u * k < n_ov && alive(ow_species(ow[k]));
+                            const uint64_t mask = __ballot(keep);
+                            const uint32_t pos = n + (uint32_t)__popcll(mask & lt);
+                            if (keep && pos < (uint32_t)CAP) { dst64[3 * pos] = ow[k][0]; dst64[3 * pos + 1] = ow[k][1]; dst64[3 * pos + 2] = ow[k][2] & ~(0xFFull << 56); }      /* pad = 0 */
+                            n += (uint32_t)__popcll(mask);
+                        }
+                    }
+                }
+                if (!in_regs)
                 for (uint32_t c0 = 0; c0 < stride; c0 += 64) {
                     const uint32_t i = c0 + lane;
                     mtb_slot16 x; x.a = 0; x.b = 0;
@@ -312,7 +392,7 @@ __global__ __launch_bounds__(64, (CAP > 192 ? 2 : 3)) void k_score_many(const mt
                     if (keep && pos < (uint32_t)CAP) put(pos, mtb_slot_unpack(x, (uint32_t)r + 1));
                     n += (uint32_t)__popcll(mask);
                 }
-                for (uint32_t c0 = 0; c0 < n_ov; c0 += 64) {
+                for (uint32_t c0 = in_regs ? 128u : 0u; c0 < n_ov; c0 += 64) {
                     const uint32_t i = c0 + lane;
                     mtb_match m; m.qinfo = 0; m.target_id = 0; m.species_id = 0; m.dna = 0; m.right_end_hamming = 0; m.hamming = 0; m.pad = 0;
                     bool keep = false;
@@ -340,6 +420,7 @@ __global__ __launch_bounds__(64, (CAP > 192 ? 2 : 3)) void k_score_many(const mt
         score_read_par<uint16_t, true, KEY64, mtb_match, true, CAP>(w.m, (int32_t)n, w, s_btax, s_bham, s_otax, s_ocnt, s_lev, s_anc, nb, read_len, tx, sp, off, room,
                                                                    tc_tax, tc_cnt, tc_cap, (mtb_match *)nullptr, R);
         if (lane == 0) { R.query_length = ql1; R.query_length2 = ql2; R.reserved = 0; R.taxcnt_off += (uint32_t)tc_base; results[r] = R; }
+    }
     }
     if (stats && lane == 0 && seen) { atomicAdd(&stats[0], seen); atomicAdd(&stats[1], kept); }
 }
