@@ -121,6 +121,9 @@ typedef struct {
      * at 4 and the range was redone on exact segments) -- and the reads k_seg_order put on its fail list (more tail matches or candidate
      * species than its LDS tables hold), which were copied to exact segments, sorted the general way and scored by a second launch */
     uint32_t lslot_tail_factor, n_lslot_big_reads;
+    /* short reads on slot segments: 1 = the batch's deferred tier (n_deferred_reads: k_score_many, k_many_sort + k_score_long) ran on the context's
+     * side stream beside k_score_fast; 0 = one kernel after another (profiling on, the partitioned path, the switches that drop a scorer) */
+    uint32_t score_overlapped;
 } mtb_batch_stats;
 
 /* the exact instantiations of the short-read join (kernels_dir.h) */

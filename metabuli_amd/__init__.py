@@ -45,7 +45,7 @@ class BatchStats(C.Structure):
                 ("n_deferred_reads", C.c_uint64), ("n_many_reads", C.c_uint64), ("n_many_matches", C.c_uint64), ("n_many_kept", C.c_uint64),
                 ("join_variant", C.c_int32), ("join_tuned", C.c_int32), ("join_tune_ms", C.c_float * 3),
                 ("join_tiles", C.c_uint32), ("join_tiles_windowed", C.c_uint32), ("join_tiles_outside", C.c_uint32),
-                ("lslot_tail_factor", C.c_uint32), ("n_lslot_big_reads", C.c_uint32)]
+                ("lslot_tail_factor", C.c_uint32), ("n_lslot_big_reads", C.c_uint32), ("score_overlapped", C.c_uint32)]
 
 
 SHARE_BYTES = 4 * 64 + 4 * 8 + 8 + 2 * 4 + 5 * 4 + 4 + 8 + 4 * 8      # sizeof(mtb_index_share) (tests/test_abi.py checks it against the header)

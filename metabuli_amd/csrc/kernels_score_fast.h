@@ -129,11 +129,16 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
         const int32_t read_len = ql1 + ql2;
         const int32_t nb = mtb_num_buckets(read_len, sp.dna_shift);
         const uint32_t cur = cursor[r];
+        /* flag 2 = the read's tail overflowed: it is on the deferred tier's list already (k_list_overflowed lists the same reads from the
+         * cursors before any scorer starts; score_fixed_slots) and the generic kernel does not look at it.  Nothing of it is loaded here.
+         * (No shared counter here: millions of returning atomics on one address cost tens of ms -- the generic kernel appended 1.1 M such
+         * reads to its list one atomic each, 11 of its 12.7 ms.) */
+        if (cur > tail_cap) { MTB_FAST_COUNT(0, 1); if (lane == 0) slow_flag[r] = 2; continue; }
         const mtb_slot16 *slots = slots_all + r * (uint64_t)stride;
         mtb_slot16 x[KL];
 #pragma unroll
         for (int k = 0; k < KL; k++) { const uint32_t i = (uint32_t)lane + 64u * k; x[k].a = 0; x[k].b = 0; if (i < stride) x[k] = slots[i]; }
-        bool slow = cur > tail_cap || nb > MTB_FAST_BKT;
+        bool slow = nb > MTB_FAST_BKT;
         wave_fence();                                   /* previous read's LDS traffic is complete */
         MTB_FAST_MARK(0);       /* setup + slot loads issued */
         /* ---- compaction of the live slots -> keys / aux in LDS, ordered by (species, slot order).  A stray match of a foreign
@@ -306,7 +311,7 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
         const int32_t nslot = (n + 63) >> 6;
         bool bad = false, bad2 = false;
 #ifdef MTB_FAST_DEBUG
-        if (slow) MTB_FAST_COUNT(cur > tail_cap || nb > MTB_FAST_BKT ? 0 : 1, 1);
+        if (slow) MTB_FAST_COUNT(nb > MTB_FAST_BKT ? 0 : 1, 1);
 #endif
 #pragma unroll
         for (int k = 0; k < K; k++) {
@@ -352,10 +357,7 @@ __global__ __launch_bounds__(64, K <= 3 ? 5 : 4) void k_score_fast(const mtb_slo
         if (!slow) { if (__any(bad)) MTB_FAST_COUNT(2, 1); else if (__any(bad2)) MTB_FAST_COUNT(3, 1); }
 #endif
         slow = slow || __any(bad || bad2);
-        /* flag 2 = the read's tail overflowed: it is listed for the deferred path (k_list_flag2) and the generic kernel does not look at it.
-         * (No shared counter here: millions of returning atomics on one address cost tens of ms -- the generic kernel appended 1.1 M such
-         * reads to its list one atomic each, 11 of its 12.7 ms.) */
-        if (slow) { if (lane == 0) slow_flag[r] = cur > tail_cap ? 2 : 1; continue; }
+        if (slow) { if (lane == 0) slow_flag[r] = 1; continue; }         /* (tail overflow, flag 2: left above) */
         if (lane == 0) cnt_out[r] = (uint32_t)n_live;
         MTB_FAST_MARK(2);       /* own elements, flags, links */
         /* ---- chain DP as one segmented prefix sum; candidates for emission ---- */

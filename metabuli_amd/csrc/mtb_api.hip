@@ -106,6 +106,14 @@ struct DevBuf { void *p = nullptr; size_t cap = 0; BufKind kind = BUF_WORK; };
 #define MTB_SLAB_POOL_MAX (16ull << 30)
 #define MTB_LONG_WIN_MAX_PER_Q 24.0   /* long reads: targets per query metamer up to which the window form is taken without being asked for */
 #define MTB_OVF_STRIPES 256u
+/* score stage of a short-read batch: the deferred tier beside k_score_fast on a side stream (score_fixed_slots); 0 = one stream, one kernel after
+ * another (what a context with profiling on does in any build).  k_score_many's workgroups per CU while it shares the CUs. */
+#ifndef MTB_SCORE_OVERLAP
+#define MTB_SCORE_OVERLAP 1
+#endif
+#ifndef MTB_SCORE_OVERLAP_GRID
+#define MTB_SCORE_OVERLAP_GRID 4u
+#endif
 
 /* The context's device scalars (mtb_ctx::d_scal), one 8-byte word per name.  Names cleared or read back with ONE call stay adjacent; two names share a word only where noted. */
 enum Scal : uint32_t {
@@ -172,6 +180,10 @@ struct mtb_ctx {
      * queued copies, and which of the two device-side result buffer sets the next call writes */
     hipStream_t down_stream = nullptr; hipEvent_t down_ready = nullptr, down_done = nullptr; bool down_pending = false; int res_set = 0;
     int pk_set = 0;                                  /* the set the last classify call read */
+    /* the deferred tier of a short-read batch beside k_score_fast (score_fixed_slots): a side stream made right after the compute stream, so that the
+     * two take neighbouring hardware queues, and the events of the fork (0), of the tier's first scorer being queued (1) and of the tier's end (2) */
+    hipStream_t side_stream = nullptr; hipEvent_t side_ev[3] = {nullptr, nullptr, nullptr};
+    uint32_t score_overlapped = 0;                   /* last slot-path batch: its deferred tier ran on the side stream */
     /* one record per set.  The protocol of mtb.h is prefetch(k+1), classify(k): when batch k+1 is prefetched, batch k (prefetched one call
      * earlier) is still waiting for its classify call, so TWO prefetches are outstanding for a moment -- with a single record classify(k)
      * found batch k+1's key, discarded it and uploaded k again */
@@ -422,6 +434,18 @@ void mtb_default_params(mtb_params *p) {   /* setClassifyDefaults, classify.cpp:
     p->min_score = 0.0f; p->min_sp_score = 0.0f; p->tie_ratio = 0.95f; p->accession_level = 0; p->skip_redundancy = 0;
 }
 
+/* the side stream of the score stage and its events (mtb_ctx::side_stream); called right after the context's compute stream exists (a lane's: the two are
+ * created one after the other; a caller's stream: whenever the caller made it).  Leaves nothing behind when it fails. */
+static hipError_t make_side_stream(mtb_ctx *c) {
+    hipError_t e = hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { c->side_stream = nullptr; return e; }
+    for (int k = 0; k < 3 && e == hipSuccess; k++) { e = hipEventCreateWithFlags(&c->side_ev[k], hipEventDisableTiming); if (e != hipSuccess) c->side_ev[k] = nullptr; }
+    if (e != hipSuccess) {
+        for (int k = 0; k < 3; k++) if (c->side_ev[k]) { hipError_t e2 = hipEventDestroy(c->side_ev[k]); (void)e2; c->side_ev[k] = nullptr; }
+        hipError_t e2 = hipStreamDestroy(c->side_stream); (void)e2; c->side_stream = nullptr;
+    }
+    return e;
+}
 mtb_status mtb_ctx_create(int device, void *stream, mtb_ctx **out) {
     if (!out) return fail(MTB_ERR_ARG, "out is NULL");
     int n = 0;
@@ -431,6 +455,8 @@ mtb_status mtb_ctx_create(int device, void *stream, mtb_ctx **out) {
     HIPCHK(hipSetDevice(device));
     mtb_ctx *c = new mtb_ctx();
     c->device = device; c->stream = (hipStream_t)stream;
+    {   const hipError_t es = make_side_stream(c);          /* before anything else the context owns: a failure here leaves nothing to free but the object */
+        if (es != hipSuccess) { delete c; return fail(MTB_ERR_DEVICE, std::string("side stream of the score stage: ") + hipGetErrorString(es)); } }
     mtb_build_tables(&c->h_tabs);
     HIPCHK(hipMalloc((void **)&c->d_tabs, sizeof(mtb_tables)));
     HIPCHK(hipMemcpy(c->d_tabs, &c->h_tabs, sizeof(mtb_tables), hipMemcpyHostToDevice));
@@ -458,6 +484,8 @@ void mtb_ctx_destroy(mtb_ctx *c) {
     if (c->down_ready) e = hipEventDestroy(c->down_ready);
     if (c->down_done) e = hipEventDestroy(c->down_done);
     if (c->copy_stream) { e = hipStreamSynchronize(c->copy_stream); e = hipStreamDestroy(c->copy_stream); }
+    if (c->side_stream) { e = hipStreamSynchronize(c->side_stream); e = hipStreamDestroy(c->side_stream); }
+    for (int k = 0; k < 3; k++) if (c->side_ev[k]) e = hipEventDestroy(c->side_ev[k]);
     for (int k = 0; k < 2; k++) { if (c->copy_done[k]) e = hipEventDestroy(c->copy_done[k]); if (c->unpacked[k]) e = hipEventDestroy(c->unpacked[k]); }
     for (int q = 0; q < 4; q++) if (c->join_tunes[q].e0) { e = hipEventDestroy(c->join_tunes[q].e0); e = hipEventDestroy(c->join_tunes[q].e1); }
     for (int i = 0; i < 8; i++) e = hipEventDestroy(c->ev[i]);
@@ -505,6 +533,7 @@ mtb_status mtb_ctx_set_streams(mtb_ctx *c, int n) {
         mtb_ctx *l = new mtb_ctx();
         l->device = c->device; l->is_lane = true; l->d_tabs = c->d_tabs; l->h_tabs = c->h_tabs; l->profiling = c->profiling; l->placement_probe = c->placement_probe; l->opt = c->opt;
         HIPCHK(hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking));
+        HIPCHK(make_side_stream(l));
         HIPCHK(hipMalloc((void **)&l->d_scal, SC_WORDS * sizeof(uint64_t)));
         HIPCHK(hipMalloc((void **)&l->d_ovfctr, MTB_OVF_STRIPES * 64));
         for (int i = 0; i < 8; i++) HIPCHK(hipEventCreate(&l->ev[i]));
@@ -519,11 +548,12 @@ mtb_status mtb_ctx_set_streams(mtb_ctx *c, int n) {
 /* ------------------------------------------------------------------ */
 /* internal device-side stages                                         */
 /* ------------------------------------------------------------------ */
-static mtb_status d2h(mtb_ctx *c, void *dst, const void *src, size_t bytes) {
-    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+static mtb_status d2h(mtb_ctx *c, void *dst, const void *src, size_t bytes, hipStream_t st) {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return MTB_OK;
 }
+static mtb_status d2h(mtb_ctx *c, void *dst, const void *src, size_t bytes) { return d2h(c, dst, src, bytes, c->stream); }
 static mtb_status h2d(mtb_ctx *c, void *dst, const void *src, size_t bytes) {
     if (bytes == 0) return MTB_OK;
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
@@ -1038,6 +1068,7 @@ struct ScoreSrc {
     const uint8_t *only_flagged = nullptr; /* slot mode after k_score_fast: score only the reads it flagged */
     const uint32_t *seg_cnt = nullptr;     /* slab launches: matches per read when the segment does not fill [seg[r], seg[r + 1]) */
     const void *bound_by_buckets = nullptr; /* non-NULL: every read gets one taxcnt slot per position bucket (its match count is not in seg[]) */
+    bool overflowed_listed = false;         /* slot mode: the caller lists the reads k_score_fast flags 2 itself (k_list_overflowed); big_list takes only what the generic kernel defers */
 };
 
 /* d_results/d_tc_* are device outputs; *n_tc = sum of per-read bounds.  `second` (optional) runs after the launch
@@ -1045,6 +1076,12 @@ struct ScoreSrc {
  * have it launched with the same per-read taxcnt slots. */
 struct ScoreLaunch { const uint64_t *d_tcoff; bool key64; mtb_score_params sp; ReadLens lens; ResultSink out; };     /* what dev_score has set up by the time `second` runs: enough to launch a scorer of its own */
 typedef std::function<mtb_status(ScoreSrc *, bool *, const ScoreLaunch &)> ScoreSecond;
+typedef std::function<mtb_status(const ScoreLaunch &)> ScoreFork;       /* optional: runs once the taxcnt layout exists, before the first scorer is launched (score_fixed_slots starts its deferred tier there) */
+/* dev_score takes a slot batch's reads through the register-resident scorer first */
+static bool fast_scorer_applies(const mtb_ctx *c, const mtb_index *ix, const mtb_params *p, const ReadLens &lens, uint32_t stride) {
+    const bool key64 = ix->tax.max_id < (1 << 22) && lens.max_len + 3 < (1u << 11);
+    return key64 && stride <= 384u && !c->opt.no_fast_scorer && !(p->seq_mode == 2 && c->opt.no_fast_pairs);
+}
 /* per-read bounds of the taxcnt slots (k_taxcnt_bound over seg / cnt) -> d_tcoff (n_reads + 1); *n_tc = their sum, checked against the sink */
 static mtb_status taxcnt_layout(mtb_ctx *c, uint64_t n_reads, const uint64_t *d_seg, const uint32_t *d_cnt, const ReadLens &lens, const ResultSink &out, int dna_shift, uint64_t *d_tcoff, uint64_t *n_tc) {
     uint32_t *d_bound; uint64_t *d_ws;
@@ -1057,7 +1094,7 @@ static mtb_status taxcnt_layout(mtb_ctx *c, uint64_t n_reads, const uint64_t *d_
     return MTB_OK;
 }
 static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const ReadLens &lens, const ResultSink &out, uint64_t *n_tc,
-                            const ScoreSrc &first, const ScoreSecond *second) {
+                            const ScoreSrc &first, const ScoreSecond *second, const ScoreFork *fork = nullptr) {
     mtb_score_params sp; mtb_make_score_params(p, &sp);
     uint64_t *d_tcoff;
     STCHK(ensure(c, "tcoff", n_reads + 1, &d_tcoff));
@@ -1067,6 +1104,14 @@ static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint
     const uint32_t max_nb_first = (uint32_t)mtb_num_buckets((int32_t)lens.max_len, sp.dna_shift);
     const uint32_t max_nb_second = (uint32_t)mtb_num_buckets((int32_t)std::max(lens.max_len, first.max_len_deferred), sp.dna_shift);
     if (max_nb_second > 65535u) return fail(MTB_ERR_ARG, "read too long for mtb_result.n_taxcnt (16 bits): more than 65535 position buckets");
+    if (fork) {
+        /* what the launches below ask for is asked for before the fork where it is known by now: an allocation synchronises the device, and the
+         * batch that grows a buffer behind the fork runs its tier after k_score_fast instead of beside it.  Left behind the fork: the slab pool of
+         * a batch with more than MTB_SCORE_BKT position buckets (reads beyond ~1100 bases among short ones; BUF_FIXED, it grows once per context). */
+        uint8_t *d_slow_early;
+        if (first.cursor && fast_scorer_applies(c, ix, p, lens, first.stride)) STCHK(ensure(c, "slowflag", n_reads, &d_slow_early));
+        STCHK((*fork)(ScoreLaunch{d_tcoff, key64, sp, lens, out}));
+    }
     ScoreSrc second_src;
     for (int pass = 0; pass < 2; pass++) {
         const uint32_t max_nb = pass ? max_nb_second : max_nb_first;
@@ -1101,7 +1146,7 @@ static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint
         out.tc_base, S->list, S->n_list, S->cursor, S->stride, S->seg_by_list, S->direct, S->epoch, S->big_list, S->n_big, S->cnt_out, d_work, S->only_flagged, S->seg_cnt)
         ScoreSrc S_rest;
         const bool pairs = p->seq_mode == 2;
-        if (S->cursor && pass == 0 && key64 && S->stride <= 384u && !c->opt.no_fast_scorer && !(pairs && c->opt.no_fast_pairs)) {
+        if (S->cursor && pass == 0 && fast_scorer_applies(c, ix, p, lens, S->stride)) {
             /* slot mode: the register-resident scorer takes every read with the common structure (slots in compareMatches order
              * once the species -- for pairs the (species, frame) runs -- are laid one after another, one match per position
              * group) and lists the others for the generic kernel below */
@@ -1116,7 +1161,7 @@ static mtb_status dev_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint
               else if (S->stride <= 128) MTB_LAUNCH_FAST(2); else if (S->stride <= 192) MTB_LAUNCH_FAST(3); else if (S->stride <= 256) MTB_LAUNCH_FAST(4); else MTB_LAUNCH_FAST(5, 6, false); }
 #undef MTB_LAUNCH_FAST
             hipLaunchKernelGGL(k_count_flags, dim3(256), dim3(256), 0, c->stream, (const uint8_t *)d_slow, n_reads, scal<unsigned long long>(c, SC_N_GENERIC));
-            if (S->big_list && S->n_big) hipLaunchKernelGGL(k_list_flag2, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_slow, n_reads, S->big_list, S->n_big);
+            if (S->big_list && S->n_big && !S->overflowed_listed) hipLaunchKernelGGL(k_list_flag2, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, c->stream, (const uint8_t *)d_slow, n_reads, S->big_list, S->n_big);
             c->fast_used = true;
             S_rest = *S; S_rest.only_flagged = d_slow;
             S = &S_rest;
@@ -2343,10 +2388,10 @@ static uint64_t ovf_cap_regrown(uint64_t n) { return n + n / 16 + 1024; }
  * register-resident scorer, the generic one for the reads it flags, exact segments for the reads neither can take from their slots.
  * *nm_out = matches seen (statistics). */
 static mtb_status score_fixed_slots(mtb_ctx *c, mtb_index *ix, const mtb_params *p, uint64_t n_reads, const ReadLens &lens, uint64_t nk_real, const SlotSegs &sl,
-                                    const ResultSink &out, uint64_t *n_taxcnt, uint64_t *nm_out) {
+                                    const ResultSink &out, uint64_t *n_taxcnt, uint64_t *nm_out, bool may_overlap = true) {
     hipStream_t st = c->stream;
     uint64_t nm = 0;
-    memset(c->many_stats, 0, sizeof(c->many_stats));
+    memset(c->many_stats, 0, sizeof(c->many_stats)); c->score_overlapped = 0;
     uint32_t *d_biglist, *d_bigcnt, *d_bigidx, *d_bigcur, *d_cnt; uint64_t *d_bigstart = nullptr, *d_ws2, *d_tot; mtb_match *d_big = nullptr;
     STCHK(ensure(c, "biglist", n_reads, &d_biglist)); STCHK(ensure(c, "bigidx", n_reads, &d_bigidx)); STCHK(ensure(c, "livecnt", n_reads, &d_cnt));
     STCHK(ensure(c, "segstart", n_reads + 1, &d_tot)); STCHK(ensure(c, "scanws", scan_ws_elems(n_reads + 1), &d_ws2));
@@ -2363,88 +2408,173 @@ static mtb_status score_fixed_slots(mtb_ctx *c, mtb_index *ix, const mtb_params 
     }
     a.max_seg = a.cap;
     a.big_list = d_biglist; a.n_big = scal<uint32_t>(c, SC_N_DEFERRED); a.cnt_out = d_cnt;
-    /* reads the first launch could not take from their slots: exact segments (live slots + overflow list), sorted in HBM */
+    /* ---- the deferred tier: the reads of conserved genes (kernels_score_many.h), scored straight from their slots + their overflow entries, dead
+     * species dropped before anything is ordered; what k_score_many hands on goes through k_many_sort + k_score_long; what is left after both
+     * takes the exact-segment path below.  Two lists come here:
+     *   A  the reads whose tails overflowed, {r : cursor[r] > tail_cap} -- known from the join's cursors before any scorer runs (k_list_overflowed;
+     *      k_score_fast flags exactly these 2 and touches nothing else of them), length in a word of its own (d_ms[MS_N_A]);
+     *   B  the reads the generic slot kernel could not stage (d_biglist / SC_N_DEFERRED, appended to while that kernel runs).
+     * `early` batches run the tier for A BESIDE k_score_fast on the context's side stream: the tier's kernels wait on memory with the VALUs
+     * three quarters idle, k_score_fast is bound by VALU issue, the two sets of reads are disjoint and every output is per read.  The side
+     * stream forks once the taxcnt layout exists, the compute stream is held until the tier's first scorer is queued (its few fat workgroups
+     * must be resident before the flood of k_score_fast's thin ones), and joins before list B is looked at.  With profiling on (and in
+     * -DMTB_SCORE_OVERLAP=0 builds) the same launches run on the compute stream in the same order: per-kernel times stay solo times.
+     * Long reads never come here; the partitioned path (may_overlap = false), MTB_NO_FAST_SCORER, MTB_NO_FAST_PAIRS on pairs and strides beyond 384
+     * keep the serial order of old -- k_score_fast, k_list_flag2, the generic kernel, then the tier over ONE list -- and MTB_NO_SCORE_MANY has no tier. ---- */
+    const bool tiers = !c->opt.no_score_many && sl.stride <= 384u;
+    const bool early = tiers && may_overlap && fast_scorer_applies(c, ix, p, lens, sl.stride);
+    const bool overlap = early && MTB_SCORE_OVERLAP != 0 && !c->profiling && c->side_stream != nullptr;
+    const bool have_ovf = sl.ovf_region ? c->ovf_max_region != 0 : sl.n_ovf != 0;
+    const bool cap192 = c->opt.many_cap ? c->opt.many_cap <= 192 : sl.stride <= 192u;
+    enum { MS_REST = 0, MS_WORK = 1, MS_STATS = 2, MS_LONG_WORK = 8, MS_N_FIN = 9, MS_N_A = 15, MS_RUN = 16 };      /* words of a run's block of d_ms; MS_N_FIN and MS_N_A: first block only */
+    unsigned long long *d_ms = nullptr;          /* two blocks of MS_RUN words: the run over list A (or the only run), the run over list B */
+    uint32_t *d_alist = nullptr, *d_rest[2] = {nullptr, nullptr}, *d_fin = nullptr, *d_novf = nullptr, *d_ocur = nullptr, *d_bc3 = nullptr, *d_segcnt = nullptr;
+    uint64_t *d_ostart = nullptr, *d_bs3 = nullptr, *d_wss = d_ws2; uint8_t *d_todo = nullptr;
+    mtb_match *d_ovfg = nullptr;                 /* the overflow list grouped by read, once the tier has built it */
+    bool grouped = false, many_timed = false, sort_on = false;
+    uint32_t n_a = 0, n_fin = 0, n_rest_all = 0;     /* reads of list A; reads no tier scored so far; reads k_score_many handed on so far */
+    /* the tier's buffers.  Early batches ask for all of them before the fork, sized by the batch: an allocation synchronises the device.
+     * (Not "manym", the handed-on reads' segments: its size is a read-back of the tier's.  It comes out of the join's dead buffers; a batch
+     * that outgrows them allocates once, and that one batch's tier waits for k_score_fast.) */
+    auto tier_buffers = [&](uint64_t n_sort) -> mtb_status {
+        if (d_ms) return MTB_OK;
+        STCHK(ensure(c, "manystat", 2 * MS_RUN, &d_ms)); STCHK(ensure(c, "restlist", n_reads, &d_rest[0])); STCHK(ensure(c, "restlist2", n_reads, &d_fin));
+        if (early) { STCHK(ensure(c, "overflowed", n_reads, &d_alist)); STCHK(ensure(c, "restlistb", n_reads, &d_rest[1])); STCHK(ensure(c, "scanwsside", scan_ws_elems(n_reads + 1), &d_wss)); }
+        if (have_ovf) {
+            STCHK(ensure(c, "novf", n_reads, &d_novf)); STCHK(ensure(c, "ocur", n_reads, &d_ocur)); STCHK(ensure(c, "ovfstart", n_reads + 1, &d_ostart));
+            STCHK(scratch(c, "ovfg", sl.n_ovf + 1, &d_ovfg));
+        }
+        STCHK(ensure(c, "bigcnt", n_sort, &d_bc3)); STCHK(ensure(c, "bigstart", n_sort + 1, &d_bs3)); STCHK(ensure(c, "bigseg", n_sort, &d_segcnt));
+        STCHK(ensure(c, "todoflag", n_reads, &d_todo));
+        HIPCHK(hipMemsetAsync(d_ms, 0, 2 * MS_RUN * 8, st));
+        return MTB_OK;
+    };
+    /* the overflow list grouped by read (counts from the tail cursors); built once, by whichever run comes first */
+    auto group_ovf = [&](hipStream_t sq) -> mtb_status {
+        if (!have_ovf || grouped) return MTB_OK;
+        grouped = true;
+        HIPCHK(hipMemsetAsync(d_ocur, 0, n_reads * 4, sq));
+        hipLaunchKernelGGL(k_ovf_count, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, sq, (const uint32_t *)sl.d_rc, sl.d_off_reads, n_reads, sl.stride - sl.direct, d_novf);
+        scan_launch<uint32_t, uint64_t, false>(sq, d_novf, n_reads, true, d_ostart, d_wss);
+        if (sl.ovf_region) hipLaunchKernelGGL(k_ovf_group, dim3((uint32_t)((c->ovf_max_region + 255) / 256), MTB_OVF_STRIPES), dim3(256), 0, sq, (const mtb_match *)sl.d_ovf, sl.n_ovf,
+                                           (const uint64_t *)d_ostart, (const uint32_t *)d_novf, d_ocur, d_ovfg, sl.ovf_region, (const unsigned long long *)c->d_ovfctr);
+        else hipLaunchKernelGGL(k_ovf_group, dim3((uint32_t)((sl.n_ovf + 255) / 256)), dim3(256), 0, sq, (const mtb_match *)sl.d_ovf, sl.n_ovf,
+                                (const uint64_t *)d_ostart, (const uint32_t *)d_novf, d_ocur, d_ovfg, (uint64_t)0, (const unsigned long long *)nullptr);
+        return MTB_OK;
+    };
+    /* one run of the tier over a list whose length sits on the device.  run 0: list A (or the only list), run 1: list B behind it.
+     * tier_begin queues k_score_many; tier_end reads its counters back (synchronising ONLY the run's stream), takes what it handed on
+     * through k_many_sort + k_score_long and appends what is still unscored to the final list d_fin / d_ms[MS_N_FIN]. */
+    auto tier_begin = [&](int run, hipStream_t sq, const uint32_t *d_list, const uint32_t *d_n, uint32_t grid, const ScoreLaunch &SL) -> mtb_status {
+        unsigned long long *ms = d_ms + run * MS_RUN;
+        sort_on = SL.key64 && !c->opt.no_many_sort;
+        /* without the second tier kernels the hand-over list IS the final list: both runs append to the first one's */
+        uint32_t *rest = sort_on ? d_rest[run] : d_rest[0]; uint32_t *n_rest = (uint32_t *)((sort_on ? ms : d_ms) + MS_REST);
+#define MTB_LAUNCH_MANY(K64, CAPV) hipLaunchKernelGGL((k_score_many<K64, CAPV>), dim3(grid), dim3(64), 0, sq, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads, \
+        (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, d_list, d_n, SL.lens.d_ql, SL.lens.d_ql2, tax_view(ix), SL.sp, SL.d_tcoff, SL.out.d_res, \
+        SL.out.d_tc_tax, SL.out.d_tc_cnt, SL.out.tc_cap, SL.out.tc_base, rest, n_rest, d_cnt, ms + MS_WORK, ms + MS_STATS)
+        if (cap192) { if (SL.key64) MTB_LAUNCH_MANY(true, 192); else MTB_LAUNCH_MANY(false, 192); }
+        else { if (SL.key64) MTB_LAUNCH_MANY(true, 320); else MTB_LAUNCH_MANY(false, 320); }
+#undef MTB_LAUNCH_MANY
+        HIPCHK(hipGetLastError());
+        return MTB_OK;
+    };
+    auto tier_end = [&](int run, hipStream_t sq, uint32_t n_list, const ScoreLaunch &SL) -> mtb_status {
+        unsigned long long *ms = d_ms + run * MS_RUN;
+        uint64_t h[2 * MS_RUN];
+        STCHK(d2h(c, h, d_ms, sizeof(h), sq));
+        const uint64_t *hr = h + run * MS_RUN;
+        if (run == 0 && early) n_list = n_a = (uint32_t)(h[MS_N_A] & 0xFFFFFFFFull);
+        const uint32_t rest_seen = (uint32_t)((sort_on ? hr[MS_REST] : h[MS_REST]) & 0xFFFFFFFFull);
+        const uint32_t n_rest = sort_on ? rest_seen : rest_seen - n_rest_all;
+        n_rest_all += n_rest;
+        c->many_stats[2] += hr[MS_STATS]; c->many_stats[3] += hr[MS_STATS + 1];
+        if (c->opt.many_verbose) fprintf(stderr, "mtb: k_score_many: %u reads listed, %u handed on (routed off / buckets / counts %llu, species table full %llu, survivors beyond the staging %llu); %llu matches, %llu survive the dead-species drop\n",
+                                                n_list, n_rest, (unsigned long long)hr[MS_STATS + 2], (unsigned long long)hr[MS_STATS + 3], (unsigned long long)hr[MS_STATS + 4], (unsigned long long)hr[MS_STATS], (unsigned long long)hr[MS_STATS + 1]);
+        if (!sort_on) { n_fin = n_rest_all; return MTB_OK; }
+        if (!n_rest) return MTB_OK;
+        /* ---- reads beyond the staging (thousands of matches: conserved genes of organisms that are not in the index): a workgroup per
+         * read gathers, drops dead species, sorts in LDS and writes the read's exact segment; k_score_long streams it ---- */
+        const uint32_t *d_r = d_rest[run]; mtb_match *d_big3;
+        if (!early) { STCHK(ensure(c, "bigcnt", n_rest, &d_bc3)); STCHK(ensure(c, "bigstart", (uint64_t)n_rest + 1, &d_bs3)); STCHK(ensure(c, "bigseg", n_rest, &d_segcnt)); }
+        hipLaunchKernelGGL(k_big_count, dim3(std::min<uint32_t>(n_rest, 4096)), dim3(64), 0, sq, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch,
+                           (const uint32_t *)sl.d_rc, d_r, n_rest, d_bc3, d_bigidx, scal<uint32_t>(c, SC_MAX_BIG_SEG), sl.d_off_reads);
+        scan_launch<uint32_t, uint64_t, false>(sq, d_bc3, n_rest, true, d_bs3, d_wss);
+        uint64_t total3 = 0;
+        STCHK(d2h(c, &total3, d_bs3 + n_rest, 8, sq));
+        STCHK(scratch(c, "manym", total3 + 1, &d_big3));
+        HIPCHK(hipMemsetAsync(d_todo, 0, n_reads, sq));
+        /* the small instantiation first (20 KB of LDS: eight workgroups per CU), the big one for the reads it flags 2 */
+        hipLaunchKernelGGL((k_many_sort<11, 2048u>), dim3(std::min<uint32_t>(n_rest, 256u * 8u)), dim3(MTB_MSORT_NT), 0, sq, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads,
+                           (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, d_r, n_rest, SL.lens.d_ql, SL.lens.d_ql2, SL.sp.dna_shift, (const uint64_t *)d_bs3, d_big3, d_segcnt, d_todo, 0u, 2u);
+        hipLaunchKernelGGL((k_many_sort<12, 4096u>), dim3(std::min<uint32_t>(n_rest, 256u * 3u)), dim3(MTB_MSORT_NT), 0, sq, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads,
+                           (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, d_r, n_rest, SL.lens.d_ql, SL.lens.d_ql2, SL.sp.dna_shift, (const uint64_t *)d_bs3, d_big3, d_segcnt, d_todo, 2u, 1u);
+        hipLaunchKernelGGL((k_score_long<2048, 256, 256, 256>), dim3(std::min<uint32_t>(n_rest, 256u * 5u)), dim3(MTB_LONG_NT), 0, sq, (const mtb_match *)d_big3, (const uint64_t *)d_bs3, n_reads, SL.lens.d_ql, SL.lens.d_ql2,
+                           tax_view(ix), SL.sp, SL.d_tcoff, SL.out.d_res, SL.out.d_tc_tax, SL.out.d_tc_cnt, SL.out.tc_cap, SL.out.tc_base, d_todo, ms + MS_LONG_WORK, (const uint32_t *)d_segcnt, d_r, n_rest);
+        hipLaunchKernelGGL(k_list_flagged, dim3((n_rest + 255) / 256), dim3(256), 0, sq, d_r, n_rest, (const uint8_t *)d_todo, (const uint32_t *)d_bc3, d_fin, (uint32_t *)(d_ms + MS_N_FIN), d_cnt);
+        HIPCHK(hipGetLastError());
+        uint64_t left = 0;
+        STCHK(d2h(c, &left, d_ms + MS_N_FIN, 8, sq));
+        if (c->opt.many_verbose) fprintf(stderr, "mtb: k_many_sort + k_score_long: %u reads (%llu records), %llu in all left for the exact-segment path\n", n_rest, (unsigned long long)total3, (unsigned long long)(left & 0xFFFFFFFFull));
+        n_fin = (uint32_t)(left & 0xFFFFFFFFull);
+        return MTB_OK;
+    };
+    /* early batches: list A and its run of the tier, queued before the first scorer (dev_score calls this once the taxcnt layout exists) */
+    ScoreFork fork = [&](const ScoreLaunch &SL) -> mtb_status {
+        STCHK(tier_buffers(n_reads));
+        hipStream_t ss = overlap ? c->side_stream : st;
+        if (overlap) { HIPCHK(hipEventRecord(c->side_ev[0], st)); HIPCHK(hipStreamWaitEvent(ss, c->side_ev[0], 0)); }
+        hipLaunchKernelGGL(k_list_overflowed, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, ss, (const uint32_t *)sl.d_rc, n_reads, sl.stride - sl.direct, d_alist, (uint32_t *)(d_ms + MS_N_A));
+        if (!overlap) {
+            /* serial: the whole run here, and only if there is a list (the launch statistics count the tier once per batch that has deferred reads) */
+            uint64_t na = 0;
+            STCHK(d2h(c, &na, d_ms + MS_N_A, 8));
+            n_a = (uint32_t)na;
+            if (!n_a) return MTB_OK;
+            KTimer ktm(c, MTB_K_SCORE_MANY); many_timed = true;
+            STCHK(group_ovf(ss));
+            STCHK(tier_begin(0, ss, d_alist, (const uint32_t *)(d_ms + MS_N_A), std::min<uint32_t>((uint32_t)na, 256u * (cap192 ? 12u : 7u)), SL));
+            return tier_end(0, ss, (uint32_t)na, SL);
+        }
+        STCHK(group_ovf(ss));
+        /* a fixed grid of a few workgroups per CU (k_score_many claims blocks of reads from a counter and needs no host-side count), and the
+         * compute stream held until it is queued.  256 x 4 by measurement (2: +10.6 ms, 6 / 8 / 12: +0.35 / 0.65 / 1.0 ms): profiles/score_overlap_notes.md */
+        HIPCHK(hipEventRecord(c->side_ev[1], ss));
+        STCHK(tier_begin(0, ss, d_alist, (const uint32_t *)(d_ms + MS_N_A), 256u * MTB_SCORE_OVERLAP_GRID, SL));
+        HIPCHK(hipStreamWaitEvent(st, c->side_ev[1], 0));
+        c->score_overlapped = 1;
+        return MTB_OK;
+    };
+    /* reads the first launches could not take from their slots: the tier for list B, then exact segments (live slots + overflow list), sorted in HBM */
     ScoreSecond second = [&](ScoreSrc *b, bool *go, const ScoreLaunch &SL) -> mtb_status {
+        if (overlap) {        /* the side stream's part ends here; its read-backs wait for that stream alone */
+            STCHK(tier_end(0, c->side_stream, 0, SL));
+            HIPCHK(hipEventRecord(c->side_ev[2], c->side_stream)); HIPCHK(hipStreamWaitEvent(st, c->side_ev[2], 0));
+        }
         uint64_t sc = 0;
         STCHK(d2h(c, &sc, scal<uint64_t>(c, SC_N_DEFERRED), 8));
-        uint32_t n_big = (uint32_t)sc;
+        const uint32_t n_b = (uint32_t)sc;
+        uint32_t n_big = n_a + n_b;
         *go = n_big != 0;
         if (!n_big) return MTB_OK;
         c->many_stats[0] = n_big; c->many_stats[1] = 0;
-        const bool no_many = c->opt.no_score_many != 0;        /* A/B switch: every deferred read through exact segments (round 4's path) */
-        uint32_t *d_novf = nullptr; uint64_t *d_ostart = nullptr; mtb_match *d_ovfg = nullptr;      /* the overflow list grouped by read, once the many-species path has built it */
-        if (!no_many && sl.stride <= 384u) {
-            /* ---- the reads of conserved genes (kernels_score_many.h): scored straight from their slots + their overflow entries, dead
-             * species dropped before anything is ordered.  The overflow list is grouped by read first (counts from the tail cursors). ---- */
-            KTimer ktm(c, MTB_K_SCORE_MANY);
-            uint32_t *d_ocur = nullptr, *d_rest;
-            STCHK(ensure(c, "restlist", n_reads, &d_rest));
-            const bool have_ovf = sl.ovf_region ? c->ovf_max_region != 0 : sl.n_ovf != 0;
-            if (have_ovf) {
-                STCHK(ensure(c, "novf", n_reads, &d_novf)); STCHK(ensure(c, "ocur", n_reads, &d_ocur)); STCHK(ensure(c, "ovfstart", n_reads + 1, &d_ostart));
-                STCHK(scratch(c, "ovfg", sl.n_ovf + 1, &d_ovfg));
-                HIPCHK(hipMemsetAsync(d_ocur, 0, n_reads * 4, st));
-                hipLaunchKernelGGL(k_ovf_count, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, st, (const uint32_t *)sl.d_rc, sl.d_off_reads, n_reads, sl.stride - sl.direct, d_novf);
-                scan_launch<uint32_t, uint64_t, false>(st, d_novf, n_reads, true, d_ostart, d_ws2);
-                if (sl.ovf_region) hipLaunchKernelGGL(k_ovf_group, dim3((uint32_t)((c->ovf_max_region + 255) / 256), MTB_OVF_STRIPES), dim3(256), 0, st, (const mtb_match *)sl.d_ovf, sl.n_ovf,
-                                                   (const uint64_t *)d_ostart, (const uint32_t *)d_novf, d_ocur, d_ovfg, sl.ovf_region, (const unsigned long long *)c->d_ovfctr);
-                else hipLaunchKernelGGL(k_ovf_group, dim3((uint32_t)((sl.n_ovf + 255) / 256)), dim3(256), 0, st, (const mtb_match *)sl.d_ovf, sl.n_ovf,
-                                        (const uint64_t *)d_ostart, (const uint32_t *)d_novf, d_ocur, d_ovfg, (uint64_t)0, (const unsigned long long *)nullptr);
+        if (tiers) {
+            if (n_b) {
+                /* list B (every deferred read where no list A was made).  Behind a timed run over A it is booked with the large-segment path */
+                KTimer ktm(c, many_timed ? MTB_K_SEGSORT : MTB_K_SCORE_MANY);
+                STCHK(tier_buffers(1));
+                STCHK(group_ovf(st));
+                const int run = early ? 1 : 0;
+                STCHK(tier_begin(run, st, (const uint32_t *)d_biglist, scal<const uint32_t>(c, SC_N_DEFERRED), std::min<uint32_t>(n_b, 256u * (cap192 ? 12u : 7u)), SL));
+                STCHK(tier_end(run, st, n_b, SL));
             }
-            unsigned long long *d_ms;                                  /* [0] reads handed on, [1] work counter, [2] matches seen, [3] survivors, [4..6] hand-over reasons */
-            STCHK(ensure(c, "manystat", 16, &d_ms));
-            HIPCHK(hipMemsetAsync(d_ms, 0, 16 * 8, st));
-            const bool cap192 = c->opt.many_cap ? c->opt.many_cap <= 192 : sl.stride <= 192u;
-            const uint32_t gridm = std::min<uint32_t>(n_big, 256u * (cap192 ? 12u : 7u));
-#define MTB_LAUNCH_MANY(K64, CAPV) hipLaunchKernelGGL((k_score_many<K64, CAPV>), dim3(gridm), dim3(64), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads, \
-            (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_biglist, scal<const uint32_t>(c, SC_N_DEFERRED), SL.lens.d_ql, SL.lens.d_ql2, tax_view(ix), SL.sp, SL.d_tcoff, SL.out.d_res, \
-            SL.out.d_tc_tax, SL.out.d_tc_cnt, SL.out.tc_cap, SL.out.tc_base, d_rest, (uint32_t *)d_ms, d_cnt, d_ms + 1, d_ms + 2)
-            if (cap192) { if (SL.key64) MTB_LAUNCH_MANY(true, 192); else MTB_LAUNCH_MANY(false, 192); }
-            else { if (SL.key64) MTB_LAUNCH_MANY(true, 320); else MTB_LAUNCH_MANY(false, 320); }
-#undef MTB_LAUNCH_MANY
-            HIPCHK(hipGetLastError());
-            uint64_t ms4[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            STCHK(d2h(c, ms4, d_ms, 64));
-            const uint32_t n_rest = (uint32_t)(ms4[0] & 0xFFFFFFFFull);
-            c->many_stats[1] = n_big - n_rest; c->many_stats[2] = ms4[2]; c->many_stats[3] = ms4[3];
-            if (c->opt.many_verbose) fprintf(stderr, "mtb: k_score_many: %u reads listed, %u handed on (routed off / buckets / counts %llu, species table full %llu, survivors beyond the staging %llu); %llu matches, %llu survive the dead-species drop\n",
-                                                    n_big, n_rest, (unsigned long long)ms4[4], (unsigned long long)ms4[5], (unsigned long long)ms4[6], (unsigned long long)ms4[2], (unsigned long long)ms4[3]);
-            n_big = n_rest;
-            const unsigned long long *d_nleft = d_ms;                   /* where the number of reads still unscored sits on the device */
-            if (n_big && SL.key64 && !c->opt.no_many_sort) {
-                /* ---- reads beyond the staging (thousands of matches: conserved genes of organisms that are not in the index): a workgroup per
-                 * read gathers, drops dead species, sorts in LDS and writes the read's exact segment; k_score_long streams it ---- */
-                uint32_t *d_bc3, *d_segcnt, *d_rest2; uint64_t *d_bs3; uint8_t *d_todo; mtb_match *d_big3;
-                STCHK(ensure(c, "bigcnt", n_big, &d_bc3)); STCHK(ensure(c, "bigstart", (uint64_t)n_big + 1, &d_bs3)); STCHK(ensure(c, "bigseg", n_big, &d_segcnt));
-                STCHK(ensure(c, "restlist2", n_reads, &d_rest2)); STCHK(ensure(c, "todoflag", n_reads, &d_todo));
-                hipLaunchKernelGGL(k_big_count, dim3(std::min<uint32_t>(n_big, 4096)), dim3(64), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch,
-                                   (const uint32_t *)sl.d_rc, (const uint32_t *)d_rest, n_big, d_bc3, d_bigidx, scal<uint32_t>(c, SC_MAX_BIG_SEG), sl.d_off_reads);
-                scan_launch<uint32_t, uint64_t, false>(st, d_bc3, n_big, true, d_bs3, d_ws2);
-                uint64_t total3 = 0;
-                STCHK(d2h(c, &total3, d_bs3 + n_big, 8));
-                STCHK(scratch(c, "manym", total3 + 1, &d_big3));
-                HIPCHK(hipMemsetAsync(d_todo, 0, n_reads, st));
-                /* the small instantiation first (20 KB of LDS: eight workgroups per CU), the big one for the reads it flags 2 */
-                hipLaunchKernelGGL((k_many_sort<11, 2048u>), dim3(std::min<uint32_t>(n_big, 256u * 8u)), dim3(MTB_MSORT_NT), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads,
-                                   (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_rest, n_big, SL.lens.d_ql, SL.lens.d_ql2, SL.sp.dna_shift, (const uint64_t *)d_bs3, d_big3, d_segcnt, d_todo, 0u, 2u);
-                hipLaunchKernelGGL((k_many_sort<12, 4096u>), dim3(std::min<uint32_t>(n_big, 256u * 3u)), dim3(MTB_MSORT_NT), 0, st, (const mtb_slot16 *)sl.d_segm, sl.stride, sl.direct, sl.epoch, (const uint32_t *)sl.d_rc, sl.d_off_reads,
-                                   (const mtb_match *)d_ovfg, (const uint64_t *)d_ostart, (const uint32_t *)d_rest, n_big, SL.lens.d_ql, SL.lens.d_ql2, SL.sp.dna_shift, (const uint64_t *)d_bs3, d_big3, d_segcnt, d_todo, 2u, 1u);
-                hipLaunchKernelGGL((k_score_long<2048, 256, 256, 256>), dim3(std::min<uint32_t>(n_big, 256u * 5u)), dim3(MTB_LONG_NT), 0, st, (const mtb_match *)d_big3, (const uint64_t *)d_bs3, n_reads, SL.lens.d_ql, SL.lens.d_ql2,
-                                   tax_view(ix), SL.sp, SL.d_tcoff, SL.out.d_res, SL.out.d_tc_tax, SL.out.d_tc_cnt, SL.out.tc_cap, SL.out.tc_base, d_todo, d_ms + 8, (const uint32_t *)d_segcnt, (const uint32_t *)d_rest, n_big);
-                hipLaunchKernelGGL(k_list_flagged, dim3((n_big + 255) / 256), dim3(256), 0, st, (const uint32_t *)d_rest, n_big, (const uint8_t *)d_todo, (const uint32_t *)d_bc3, d_rest2, (uint32_t *)(d_ms + 9), d_cnt);
-                HIPCHK(hipGetLastError());
-                uint64_t left = 0;
-                STCHK(d2h(c, &left, d_ms + 9, 8));
-                if (c->opt.many_verbose) fprintf(stderr, "mtb: k_many_sort + k_score_long: %u reads (%llu records), %llu left for the exact-segment path\n", n_big, (unsigned long long)total3, (unsigned long long)(left & 0xFFFFFFFFull));
-                n_big = (uint32_t)(left & 0xFFFFFFFFull);
-                d_rest = d_rest2; d_nleft = d_ms + 9;
-            }
+            n_big = n_fin;
             c->many_stats[1] = c->many_stats[0] - n_big;
             *go = n_big != 0;
             if (!n_big) return MTB_OK;
             /* what is left goes the old way: the list of those reads, its length where the launches below read it */
-            d_biglist = d_rest;
-            HIPCHK(hipMemcpyAsync(scal<uint64_t>(c, SC_N_DEFERRED), d_nleft, 8, hipMemcpyDeviceToDevice, st));
+            d_biglist = sort_on ? d_fin : d_rest[0];
+            HIPCHK(hipMemcpyAsync(scal<uint64_t>(c, SC_N_DEFERRED), d_ms + (sort_on ? MS_N_FIN : MS_REST), 8, hipMemcpyDeviceToDevice, st));
         }
         KTimer kt(c, MTB_K_SEGSORT);
         HIPCHK(hipMemsetAsync(d_bigidx, 0xFF, n_reads * 4, st));        /* reads that are not listed (k_score_many took them) own entries of the overflow list too: k_big_ovf skips them */
@@ -2487,7 +2617,9 @@ static mtb_status score_fixed_slots(mtb_ctx *c, mtb_index *ix, const mtb_params 
         b->sort = false; b->max_seg = (uint32_t)mx; b->grid = std::min<uint32_t>(n_big, 256u * 14u); b->cap = 320;
         return MTB_OK;
     };
-    STCHK(dev_score(c, ix, p, n_reads, lens, out, n_taxcnt, a, &second));
+    a.overflowed_listed = early;
+    {   const mtb_status rs = dev_score(c, ix, p, n_reads, lens, out, n_taxcnt, a, &second, early ? &fork : nullptr);
+        if (rs != MTB_OK) { if (c->score_overlapped) { hipError_t e = hipStreamSynchronize(c->side_stream); (void)e; } return rs; } }       /* nothing of the batch stays in flight behind an error */
     /* number of matches (statistics): live records seen by the first launch + the deferred reads' segments */
     { KTimer kt(c, MTB_K_SCAN); scan_launch<uint32_t, uint64_t, false>(st, d_cnt, n_reads, true, d_tot, d_ws2); }
     STCHK(d2h(c, &nm, d_tot + n_reads, 8));
@@ -2945,7 +3077,7 @@ static mtb_status classify_attempt(mtb_ctx *c, mtb_index *ix, const mtb_params *
     S.n_reads = n_reads; S.n_bases = ex.n_bases; S.n_kmers = ex.nk_real; S.n_matches = nm; S.n_targets = ix->T;
     STCHK(take_generic_reads(c, n_reads, &S.n_generic_reads));
     S.n_slot_reads = (fixed || lslot) ? n_reads : 0;
-    if (fixed) { S.n_deferred_reads = c->many_stats[0]; S.n_many_reads = c->many_stats[1]; S.n_many_matches = c->many_stats[2]; S.n_many_kept = c->many_stats[3]; }
+    if (fixed) { S.n_deferred_reads = c->many_stats[0]; S.n_many_reads = c->many_stats[1]; S.n_many_matches = c->many_stats[2]; S.n_many_kept = c->many_stats[3]; S.score_overlapped = c->score_overlapped; }
     return MTB_OK;
 }
 static mtb_status classify_one(mtb_ctx *c, mtb_index *ix, const mtb_params *p, const Reads &rd, const ResultSink &out, uint64_t *n_taxcnt) {
@@ -2965,7 +3097,7 @@ static void merge_stats(mtb_batch_stats &S, const mtb_batch_stats &L) {
     S.join_variant = L.join_variant; S.join_tuned = L.join_tuned;                 /* (of the last range) */
     for (int v = 0; v < 3; v++) S.join_tune_ms[v] = L.join_tune_ms[v];
     S.join_tiles += L.join_tiles; S.join_tiles_windowed += L.join_tiles_windowed; S.join_tiles_outside += L.join_tiles_outside;
-    S.lslot_tail_factor = L.lslot_tail_factor; S.n_lslot_big_reads += L.n_lslot_big_reads;       /* (factor: of the last range) */
+    S.score_overlapped |= L.score_overlapped; S.lslot_tail_factor = L.lslot_tail_factor; S.n_lslot_big_reads += L.n_lslot_big_reads;       /* (factor: of the last range) */
 }
 
 /* HBM-budgeted batching (the reference sizes a QuerySplit from --max-ram, QueryIndexer.cpp:62,132, and redoes
@@ -3516,7 +3648,7 @@ mtb_status mtb_part_score(mtb_ctx *c, mtb_index *ix, const mtb_params *p, mtb_ma
             ovf_cap = ovf_cap_regrown(sl.n_ovf);          /* slots written by the failed attempt are rewritten identically */
         }
         uint64_t nm = 0; memset(&c->stats, 0, sizeof(c->stats));
-        STCHK(score_fixed_slots(c, ix, p, n_reads, ReadLens{d_ql, d_ql2, c->part_max_len}, c->part_nk_real, sl, sink, n_taxcnt, &nm));
+        STCHK(score_fixed_slots(c, ix, p, n_reads, ReadLens{d_ql, d_ql2, c->part_max_len}, c->part_nk_real, sl, sink, n_taxcnt, &nm, /* the partitioned path keeps the serial order */ false));
         c->stats.n_reads = n_reads; c->stats.n_matches = nm; c->stats.n_slot_reads = n_reads; c->stats.n_kmers = c->part_nk_real;
         STCHK(take_generic_reads(c, /* left at 0 when nothing was listed */ 0, &c->stats.n_generic_reads));
         return download_packed(c, d_res, d_tt, d_tc, n_reads, results, taxcnt_tax, taxcnt_cnt, n_taxcnt);
